@@ -10,6 +10,10 @@ SGD + EMA) on a synthetic batch resident in HBM.  Metric: train images/sec =
 (one rank per GPU) or run `python bench.py --gpus N` plainly: it then starts the N ranks itself before
 touching the GPU.  Every rank trains its own shard (weak scaling) and gradients are summed with one RCCL
 all-reduce.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what takes work of its own: the
+per-launch roofline leg over the last timed steps, the held shader clock, the other workloads (`secondary`) and the CPU
+baseline.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs below).
 """
 import argparse
 import ctypes
@@ -39,6 +43,11 @@ def parse():
     ap.add_argument("--dtype", default="bf16", choices=["f32", "f32x3", "bf16", "f16"],
                     help="bf16 = bf16 matrix-core operands, f32 accumulate/statistics (configs[1]); f32 = the exact parity path")
     ap.add_argument("--fft", default="device", choices=["host", "device"])
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, < 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline leg, the held clock, the secondary workloads and the CPU baseline; "
+                         "the --no-* and --dump-layers / --dump-full options below act on these")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip the per-launch HIP-event roofline leg")
     ap.add_argument("--dump-layers", default="", help="write every tagged launch class (layer, op, images) of the sampled steps to this JSON file")
@@ -47,7 +56,10 @@ def parse():
                          "only the compact line (\"\" = no file)")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the `secondary` entries (the other BASELINE.json shapes, the f32 parity path, DeepLabV2-ResNet101 @512^2)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def cpu_model():
@@ -375,6 +387,32 @@ def held_clock_mhz(pa, pb, nb):
     return float(np.median(out)) if out else None
 
 
+DUMP_SAMPLE = 1 << 21      # elements kept of a larger array (8 MB in float32): at most 5 such arrays stay under 64 MB in all
+
+
+def dump_outputs(tr, out_dir):
+    """What a caller of the timed path holds after its last step, as out_dir/<name>.npy: the tensors SSLTrainer.step returns
+    (the four loss terms' outputs -- CE, Dice and their reduced sums --, the consistency weight, the teacher's pseudo-labels and
+    confidence mask) and the state the step updated (student and EMA-teacher parameters, the momentum buffer, both networks'
+    BatchNorm buffers).  An array of more than DUMP_SAMPLE elements is cut to the same seeded sample of flat indices in every run."""
+    last = tr.last
+    arrays = {"loss_terms": torch.stack(last["outs"]),
+              "consistency_weight": torch.tensor([last["w"]], dtype=torch.float64),
+              "pseudo_label": last["pl"], "pseudo_label_mask": last["mask"],
+              "student_params": tr.flat_p, "teacher_params": tr.flat_t, "momentum": tr.flat_v,
+              "student_buffers": torch.cat([b.detach().flatten().double() for b in tr.model.buffers()]),
+              "teacher_buffers": torch.cat([b.detach().flatten().double() for b in tr.ema_model.buffers()])}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(1337).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.flatten()[torch.from_numpy(idx).to(t.device)]
+        if t.dtype != torch.float64:
+            t = t.float()
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     a = parse()
     rank = int(os.environ.get("RANK", 0))
@@ -420,34 +458,41 @@ def main():
 
     for s in range(a.warmup):
         tr.step(*batches[s % nb], epoch_start=(s == 0))
-    lib = _lib.lib()
-    lib.ustrun_profile_stream(torch.cuda.current_stream(dev).cuda_stream, 1)   # not the batch-1 forward's side stream
+    if a.full:
+        lib = _lib.lib()
+        lib.ustrun_profile_stream(torch.cuda.current_stream(dev).cuda_stream, 1)   # not the batch-1 forward's side stream
     sync()
-    prof = not a.no_profile
+    prof = a.full and not a.no_profile
     # the HIP-event pairs around every conv launch cost ~5 % of a step, so they sample the LAST min(2, K) steps of the
     # timed region rather than all of it (the whole region is still what `value` is computed from)
     nprof = min(2, a.steps) if prof else 0
-    # the shader clock the chip HOLDS over the timed steps: two probes (s_memtime / s_memrealtime per workgroup, a ~5 us
-    # launch each) on the step's stream around the region -> d(memtime) / d(memrealtime) x 100 MHz, median over the XCDs
-    NPB = 1024
-    pa = torch.zeros(NPB * 4, dtype=torch.int64, device=dev)
-    pb = torch.zeros(NPB * 4, dtype=torch.int64, device=dev)
-    cur = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(lib.ustrun_debug_clock_probe(pa.data_ptr(), NPB, cur))
+    if a.full:
+        # the shader clock the chip HOLDS over the timed steps: two probes (s_memtime / s_memrealtime per workgroup, a ~5 us
+        # launch each) on the step's stream around the region -> d(memtime) / d(memrealtime) x 100 MHz, median over the XCDs
+        NPB = 1024
+        pa = torch.zeros(NPB * 4, dtype=torch.int64, device=dev)
+        pb = torch.zeros(NPB * 4, dtype=torch.int64, device=dev)
+        cur = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.ustrun_debug_clock_probe(pa.data_ptr(), NPB, cur))
     t0 = time.perf_counter()
     for s in range(a.steps):
         if s == a.steps - nprof:
             lib.ustrun_profile_enable(1)
         tr.step(*batches[(a.warmup + s) % nb])
-    _lib.check(lib.ustrun_debug_clock_probe(pb.data_ptr(), NPB, cur))
+    if a.full:
+        _lib.check(lib.ustrun_debug_clock_probe(pb.data_ptr(), NPB, cur))
     sync()
     dt = time.perf_counter() - t0
-    lib.ustrun_profile_enable(0)
-    clock_mhz = held_clock_mhz(pa, pb, NPB)
+    clock_mhz = None
+    if a.full:
+        lib.ustrun_profile_enable(0)
+        clock_mhz = held_clock_mhz(pa, pb, NPB)
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(tr, a.dump_outputs)             # before the roofline leg's untimed step below moves the state on
     roof = None
     if prof:
         layers = layer_table(lib, 157.3 if a.dtype == "f32" else (416.7 if a.dtype == "f32x3" else 2500.0))
@@ -551,14 +596,14 @@ def main():
                "rccl_ranks": rccl_ranks, "collective_backend": backend,
                "roofline": roof, "cpu_baseline": None,
                "parity_note": PARITY_NOTE[a.dtype]}
-        if world == 1 and not a.no_secondary:
+        if a.full and world == 1 and not a.no_secondary:
             del tr, model, ema, batches
             import gc
             gc.collect(); torch.cuda.empty_cache()
             out["secondary"] = secondary_runs(dev, lib)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.dataset)
-        if a.dump_full:
+        if a.full and a.dump_full:
             try:
                 os.makedirs(os.path.dirname(os.path.abspath(a.dump_full)), exist_ok=True)
                 with open(a.dump_full, "w") as f:

@@ -262,8 +262,11 @@ def test_deeplab_oracle_matches_reference_goldens(name, arch):
     sd = D.make_state_dict(arch, k, int(g["model_seed"]))
     pk = [kk for kk, v in sd.items() if v.is_floating_point() and "running" not in kk]
     np.testing.assert_allclose(np.array([float(sd[kk].double().sum()) for kk in pk]), g["weight_sums"], rtol=1e-12, atol=1e-12)
+    # float64 on both sides (the fixture too, tools/gen_goldens.py): in float32 the running-mean sum of a layer whose channel
+    # means nearly cancel lands on either side of 1e-4 depending on the CPU's convolution kernels
+    sd = {kk: v.double() if v.is_floating_point() else v for kk, v in sd.items()}
     gen = torch.Generator().manual_seed(int(g["input_seed"]))
-    x = torch.randint(0, 256, (n, 3, h, w), generator=gen).float() / 127.5 - 1
+    x = (torch.randint(0, 256, (n, 3, h, w), generator=gen).float() / 127.5 - 1).double()
     with torch.no_grad():
         sdf = {kk: v.clone() for kk, v in sd.items()}
         feats = D.backbone_features(x, sdf, arch, True)
@@ -272,7 +275,7 @@ def test_deeplab_oracle_matches_reference_goldens(name, arch):
         logits = D.deeplabv2_forward(x, sd, arch, True)
         flat = logits.flatten()
         idx = torch.from_numpy(g["sample_idx"])
-        # (two f32 evaluations of 53 BatchNorm layers -- explicit scale/shift here, F.batch_norm there -- differ by ~1e-4 rel)
+        # (bounds set for two f32 evaluations of 53 BatchNorm layers -- explicit scale/shift here, F.batch_norm there -- ~1e-4 rel apart)
         rl2 = lambda a, b: float(np.linalg.norm(a.astype(np.float64) - b) / np.linalg.norm(b))
         assert rl2(flat[idx].numpy(), g["sample_val"]) < 5e-4
         assert abs(float(flat.double().norm()) - float(g["logit_l2"])) <= 1e-4 * float(g["logit_l2"])

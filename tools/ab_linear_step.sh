@@ -7,7 +7,7 @@ mkdir -p $O
 for ds in MNMS prostate; do
   for rep in 1 2; do
     for fl in 1 0; do
-      USTRUN_DEBUG_FLAGS2=$fl timeout -k 10 200 python3 $R/bench.py --dataset $ds --label_bs 8 --unlabel_bs 8 --steps 20 --warmup 3 --no-secondary \
+      USTRUN_DEBUG_FLAGS2=$fl timeout -k 10 200 python3 $R/bench.py --dataset $ds --label_bs 8 --unlabel_bs 8 --steps 20 --warmup 3 --full --no-secondary \
         --no-cpu-baseline --dump-layers $O/layers_${ds}_$fl.json 2> /dev/null | python3 -c "
 import json,sys
 b=json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -190,7 +190,9 @@ def g13_unet_bilinear(name, c, k, n, h, w):
 
 def g10_deeplab(name, arch, nclass, n, h, w, seed=1337):
     """The reference's DeepLabV2 (networks/deeplabv2.py) on a seeded input: train-mode logits (samples + checksums), the
-    backbone feature norms, running-statistic sums after that call, then eval-mode logits.  The constructor always loads
+    backbone feature norms, running-statistic sums after that call, then eval-mode logits -- in FLOAT64, so that the fixture
+    carries the reference's values and not its float32 rounding (the running-mean sum of a layer whose channel means nearly
+    cancel moved by ~1.4e-4 relative between two CPUs' float32 kernels).  The constructor always loads
     ../../checkpoints/pretrained/<arch>.pth (base.py:12, resnet.py:179-181), which does not exist here: torch.load is
     stubbed to return an empty dict for the construction (load_state_dict(strict=False) then keeps the seeded init)."""
     from networks.deeplabv2 import DeepLabV2
@@ -203,8 +205,8 @@ def g10_deeplab(name, arch, nclass, n, h, w, seed=1337):
         torch.load = real_load
     wsum = weight_sums(model)
     g = torch.Generator().manual_seed(seed + 1)
-    x = torch.randint(0, 256, (n, 3, h, w), generator=g).float() / 127.5 - 1
-    model.train()
+    x = (torch.randint(0, 256, (n, 3, h, w), generator=g).float() / 127.5 - 1).double()
+    model.double().train()
     with torch.no_grad():
         feats = model.backbone.base_forward(x)
     # a fresh model for the logits so that the running statistics below are those of exactly ONE train-mode call
@@ -214,7 +216,7 @@ def g10_deeplab(name, arch, nclass, n, h, w, seed=1337):
         model = DeepLabV2(arch, nclass)
     finally:
         torch.load = real_load
-    model.train()
+    model.double().train()
     with torch.no_grad():
         logits = model(x)
     sd = model.state_dict()

@@ -12,8 +12,8 @@ run() { # name, program args...
   find $O/$name -name "*kernel_stats.csv" -exec cp {} $O/${name}_kernel_stats.csv \;
   rm -rf $O/$name
 }
-run prostate_384_b8 $R/bench.py --dataset prostate --label_bs 8 --unlabel_bs 8 --steps 6 --warmup 2 --no-secondary --no-cpu-baseline
-run mnms_288_b8 $R/bench.py --dataset MNMS --label_bs 8 --unlabel_bs 8 --steps 6 --warmup 2 --no-secondary --no-cpu-baseline
+run prostate_384_b8 $R/bench.py --dataset prostate --label_bs 8 --unlabel_bs 8 --steps 6 --warmup 2 --full --no-secondary --no-cpu-baseline
+run mnms_288_b8 $R/bench.py --dataset MNMS --label_bs 8 --unlabel_bs 8 --steps 6 --warmup 2 --full --no-secondary --no-cpu-baseline
 run deeplab_r101_512_n16_fwdbwd $R/tools/bench_deeplab.py --n 16 --hw 512 --backward --reps 3
-run fundus_256_b16_f32x3 $R/bench.py --dtype f32x3 --steps 3 --warmup 1 --no-secondary --no-cpu-baseline
+run fundus_256_b16_f32x3 $R/bench.py --dtype f32x3 --steps 3 --warmup 1 --full --no-secondary --no-cpu-baseline
 ls -la $O
