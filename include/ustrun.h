@@ -292,6 +292,23 @@ int ustrun_dice_bwd(const float* logits, const void* target, int target_is_i64, 
 int ustrun_dice_counts(const void* pred, const void* gt, int pred_is_i64, int gt_is_i64, int N,
                        int K, int HW, int by_class, int32_t* counts, ustrun_stream_t s);
 
+/* ---- per-sample surface-distance records for the medpy metrics of the reference's test(): replaces binary.hd95 / binary.asd
+ * of train.py:306-325 (train_mnms.py twin, test.py:117-136) up to the host's final square roots and divisions.
+ * pred / gt as ustrun_dice_counts takes them: f32 {0,1} planes [N,K,H,W] (by_class = 0) or class maps [N,H,W], int64 or f32,
+ * whose part c is (x == c + 1) (by_class = 1).  border(A) = A & ~erode(A) with the 4-neighbour cross and background outside
+ * the image; d2 = exact squared Euclidean distance from a border pixel of one mask to the nearest border pixel of the other.
+ * out[n][c] = one USTRUN_SURFACE_RECORD_BYTES record:
+ *   int32 {|border(P)|, |border(G)|, d2[k], d2[min(k+1, n-1)]} -- the order statistics of the union multiset of both directions,
+ *          n = |border(P)| + |border(G)|, k = floor(0.95 (n-1)) in f64 (numpy.percentile(.., 95), linear) --,
+ *   f64   sum of sqrt(d2) over border(P) (binary.asd = that / |border(P)|), a fixed-order sum: equal bits on every run.
+ * A plane with an empty prediction or an empty ground truth has no distances: both counts are reported, the rest is 0, and the
+ * host applies the reference's rules (train.py:313-315).  H, W in 1..1024, else an error.  work: 16-byte aligned,
+ * ustrun_surface_metrics_work_bytes (-1 + error for sizes out of range); out: 8-byte aligned.                               */
+#define USTRUN_SURFACE_RECORD_BYTES 24
+int64_t ustrun_surface_metrics_work_bytes(int N, int K, int H, int W);
+int ustrun_surface_metrics(const void* pred, const void* gt, int pred_is_i64, int gt_is_i64, int N, int K, int by_class,
+                           int H, int W, void* work, int64_t work_bytes, void* out, ustrun_stream_t s);
+
 /* ---- SGD(momentum, weight decay) + EMA teacher over flat buffers: train.py:512,848,87-93 ------
  * g += wd*p; v = first ? g : mu*v + g; p -= lr*v; t = alpha*t + (1-alpha)*p                    */
 /* ---- dynamic loss scale of the IEEE-half path: torch.cuda.amp.GradScaler as train.py:552,842-845 uses it, on the device.

@@ -2,11 +2,11 @@
 """test.py -- MI355X build of the reference's evaluation driver (test.py:19-250).
 
 Same command line (flag names and defaults of test.py:19-32; `--dataset` also accepts BUSI, which the reference
-trains but does not list here); additive flags: --synthetic, --test_batches, --backend_dtype, --seed.  Loads
+trains but does not list here); additive flags: --synthetic, --test_batches, --backend_dtype, --seed, --surface_metrics.  Loads
 `../model/<dataset>/<save_name>/unet_avg_dice_best_model.pth` (a plain state_dict with the reference's keys, test.py:241)
-and prints the per-domain and mean Dice of ustrun.evaluate.validate.  The dataset classes and the medpy metrics
-(jc / hd95 / asd) are outside this build: batches come from the seeded synthetic generator unless a loader is plugged
-into `make_loaders`.
+and prints the per-domain and mean Dice of ustrun.evaluate.validate; `--surface_metrics 1` adds the reference's
+dc / jc / hd / asd lines (test.py:117-136,160-176), computed on the device instead of with medpy.  The dataset classes are
+outside this build: batches come from the seeded synthetic generator unless a loader is plugged into `make_loaders`.
 """
 import argparse
 import logging
@@ -35,6 +35,7 @@ parser.add_argument('--backend_dtype', default='f32', choices=['f32', 'f32x3', '
 parser.add_argument('--seed', type=int, default=1337)
 parser.add_argument('--load_path', type=str, default='', help='state_dict file (default: the reference\'s path)')
 parser.add_argument('--backbone', default='resnet101', choices=['resnet50', 'resnet101'], help='--model deeplabv2')
+parser.add_argument('--surface_metrics', type=int, default=0, choices=[0, 1], help='1: also dc / jc / hd95 / asd per part')
 parser.add_argument('--image_size', type=int, default=0, help='patch extent override (0: the dataset default)')
 
 DOMAINS = {"fundus": 4, "prostate": 6, "MNMS": 4, "BUSI": 1}     # test.py:209-223
@@ -66,7 +67,7 @@ def main(args):
         model = UNet(n_channels=C, n_classes=K, dtype=args.backend_dtype).cuda()
     path = args.load_path or '../model/{}/{}/{}_avg_dice_best_model.pth'.format(args.dataset, args.save_name, args.model)
     model.load_state_dict(torch.load(path, map_location="cuda"))
-    return validate(args.dataset, model, make_loaders(args, C, H), epoch=args.lb_domain)
+    return validate(args.dataset, model, make_loaders(args, C, H), epoch=args.lb_domain, surface_metrics=bool(args.surface_metrics))
 
 
 if __name__ == "__main__":

@@ -93,6 +93,8 @@ SIGNATURES = {
     "ustrun_seg_loss_fwd": (i32, [fp, vp, fp, i32, i32, i32, i32, fp, fp, i64, vp]),
     "ustrun_seg_loss_bwd": (i32, [fp, vp, fp, i32, i32, i32, i32, fp, fp, f32, f32, f32, fp, vp]),
     "ustrun_dice_counts": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "ustrun_surface_metrics_work_bytes": (i64, [i32, i32, i32, i32]),
+    "ustrun_surface_metrics": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp]),
     "ustrun_sgd_ema": (i32, [fp, fp, fp, fp, i64, f32, f32, f32, i32, f32, f32, vp]),
     "ustrun_amp_check": (i32, [fp, i64, fp, vp]),
     "ustrun_sgd_ema_scaled": (i32, [fp, fp, fp, fp, i64, f32, f32, f32, i32, f32, f32, fp, vp]),

@@ -5,8 +5,11 @@ kernel: no separate normalisation pass), prediction and the per-sample overlap c
 (ustrun_pseudo_label, ustrun_dice_counts), so one [N, parts, 3] int32 copy per batch reaches the host instead of the
 logits and masks the reference moves with .cpu(); consecutive loader batches share one forward (eval mode: samples do
 not interact).  Dice and its averaging (per batch, per domain loader, over the
-domains) are the reference's.  The medpy metrics it prints beside the Dice (jc / hd95 / asd) are outside this build;
-the per-batch loss it computes is never accumulated there and is not computed here.
+domains) are the reference's.  The medpy metrics it prints beside the Dice (dc / jc / hd95 / asd, train.py:306-325) are
+optional (`validate(..., surface_metrics=True)`): borders, the exact squared distance transform and the percentile's order
+statistics run on the device (ustrun_surface_metrics) over the same coalesced batch, one more [N, parts, 6] int32 copy reaches the
+host, and utils.metrics.surface_from_records finishes them in float64; they are averaged as the Dice is.  The per-batch
+loss the reference computes is never accumulated there and is not computed here.
 """
 import logging
 
@@ -38,6 +41,16 @@ def sample_dice(dataset, pred, mask):
     return metrics.dice_from_counts(c[..., 0], c[..., 1], c[..., 2])
 
 
+def sample_metrics(dataset, pred, mask):
+    """Per-sample, per-part (dice, dc, jc, hd95, asd), [N, parts] each: the Dice of `sample_dice` and the four medpy metrics
+    of train.py:306-320 (hd95 = asd = 100 for an empty prediction; an empty ground truth raises, as medpy does)."""
+    kw = dict(by_class=True, n_classes=3) if dataset == "MNMS" else {}
+    cnt, rec = F.dice_counts(pred, mask, **kw), F.surface_metrics(pred, mask, **kw)
+    c, r = cnt.cpu().numpy(), rec.cpu().numpy()
+    cf = c.astype(np.float64)
+    return (metrics.dice_from_counts(cf[..., 0], cf[..., 1], cf[..., 2]),) + metrics.surface_from_records(r, c)
+
+
 def batch_dice(dataset, pred, mask):
     """Per-part Dice of one batch, averaged over its samples (utils/metrics.py:149-231 without ret_arr)."""
     d = sample_dice(dataset, pred, mask)
@@ -45,9 +58,11 @@ def batch_dice(dataset, pred, mask):
 
 
 @torch.no_grad()
-def validate(dataset, model, loaders, epoch=0, log=logging.info, coalesce=64):
+def validate(dataset, model, loaders, epoch=0, log=logging.info, coalesce=64, surface_metrics=False):
     """loaders: one iterable of (image, raw label) batches per domain (any device; moved to the model's).
     Returns (val_dice[parts], per_domain[domain][parts]); leaves the model in train mode, as the reference does.
+    surface_metrics=True: returns (val_dice, per_domain, extra) with extra[m] = {"val": [parts], "per_domain": [domain][parts]}
+    for m in dc, jc, hd, asd, and logs the reference's val_%s_dc / _jc / _hd / _asd lines (train.py:349-365,378-395).
 
     In eval mode the samples of a batch do not interact (BatchNorm uses the running statistics), so up to `coalesce`
     images of consecutive loader batches go through ONE forward -- the reference's `test_bs` 1 would otherwise leave the
@@ -58,23 +73,45 @@ def validate(dataset, model, loaders, epoch=0, log=logging.info, coalesce=64):
     model.eval()
     val = [0.0] * len(part)
     per_domain = []
+    names = ("dc", "jc", "hd", "asd") if surface_metrics else ()
+    xval = {m: [0.0] * len(part) for m in names}
+    xper = {m: [] for m in names}
+    xdom = {}
+    seen = [0, 0]                                           # domain, loader batches flushed in it (for error messages)
 
     def flush(pending, dom):
         if not pending:
             return 0
         image = torch.cat([b[0] for b in pending], 0) if len(pending) > 1 else pending[0][0]
         label = torch.cat([b[1] for b in pending], 0) if len(pending) > 1 else pending[0][1]
-        d = sample_dice(dataset, predict(dataset, model(image)), decode_labels(dataset, label))
+        pred, mask = predict(dataset, model(image)), decode_labels(dataset, label)
+        if surface_metrics:
+            try:
+                d, *x = sample_metrics(dataset, pred, mask)
+            except metrics.EmptyGroundTruth as e:           # e.sample counts over the coalesced loader batches
+                b, n = 0, e.sample
+                while n >= len(pending[b][0]):
+                    n -= len(pending[b][0])
+                    b += 1
+                raise metrics.EmptyGroundTruth(n, e.part, "domain %d, loader batch %d, " % (seen[0] + 1, seen[1] + b)) from None
+        else:
+            d = sample_dice(dataset, pred, mask)
         o = 0
         for b in pending:                                   # the batch's Dice = mean over ITS samples
             n = len(b[0])
             for p in range(len(part)):
                 dom[p] += float(sum(d[o:o + n, p]) / n)
+                for m, v in zip(names, x if surface_metrics else ()):
+                    xdom[m][p] += float(sum(v[o:o + n, p]) / n)
             o += n
+        seen[1] += len(pending)
         return len(pending)
 
     for i, loader in enumerate(loaders):
         dom, nb, pending, held = [0.0] * len(part), 0, [], 0
+        seen[0], seen[1] = i, 0
+        for m in names:
+            xdom[m] = [0.0] * len(part)
         for image, label in loader:
             image, label = image.to(dev), label.to(dev)
             if pending and (held + len(image) > coalesce or image.shape[1:] != pending[0][0].shape[1:]):
@@ -87,10 +124,29 @@ def validate(dataset, model, loaders, epoch=0, log=logging.info, coalesce=64):
         per_domain.append(dom)
         for p in range(len(part)):
             val[p] += dom[p]
+        for m in names:
+            xdom[m] = [d / max(nb, 1) for d in xdom[m]]
+            xper[m].append(xdom[m])
+            for p in range(len(part)):
+                xval[m][p] += xdom[m][p]
         if log:
-            log("domain%d epoch %d :\n\t%s" % (i + 1, epoch, "".join("val_%s_dice: %f, " % (n, dom[k]) for k, n in enumerate(part))))
+            log("domain%d epoch %d :\n\t%s" % (i + 1, epoch, "".join("val_%s_dice: %f, " % (n, dom[k]) for k, n in enumerate(part)))
+                + _surface_lines(part, xdom))
     model.train()
     val = [v / max(len(loaders), 1) for v in val]
+    for m in names:
+        xval[m] = [v / max(len(loaders), 1) for v in xval[m]]
     if log:
-        log("epoch %d :\n\t%s" % (epoch, "".join("val_%s_dice: %f, " % (n, val[k]) for k, n in enumerate(part))))
+        log("epoch %d :\n\t%s" % (epoch, "".join("val_%s_dice: %f, " % (n, val[k]) for k, n in enumerate(part)))
+            + _surface_lines(part, xval))
+    if surface_metrics:
+        return val, per_domain, {m: {"val": xval[m], "per_domain": xper[m]} for m in names}
     return val, per_domain
+
+
+def _surface_lines(part, x):
+    """The reference's lines behind the Dice line (train.py:353-364): dc and jc on one, hd and asd on the next."""
+    if not x:
+        return ""
+    line = lambda m: "".join("val_%s_%s: %f, " % (n, m, x[m][k]) for k, n in enumerate(part))
+    return "\n\t" + line("dc") + "\t" + line("jc") + "\n\t" + line("hd") + "\t" + line("asd")

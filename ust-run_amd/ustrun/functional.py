@@ -338,6 +338,34 @@ def dice_counts(pred, gt, by_class=False, n_classes=1):
     return counts
 
 
+SURFACE_RECORD_I32 = 6          # USTRUN_SURFACE_RECORD_BYTES / 4
+
+
+def surface_metrics(pred, gt, by_class=False, n_classes=1):
+    """Per (sample, part) surface-distance records as int32 [N,K,6] on the device (binary.hd95 / binary.asd of
+    train.py:306-325 up to the host's part, utils.metrics.surface_from_records): {|border(pred)|, |border(gt)|, d2[k], d2[k+1]}
+    and, in the last two words, the f64 sum of sqrt(d2) over the prediction's border.  pred / gt as `dice_counts` takes them,
+    with the two image axes last."""
+    lib = L.lib()
+    pred, gt = pred.contiguous(), gt.contiguous()
+    N, (H, W) = pred.shape[0], pred.shape[-2:]
+    if pred.dim() < 3 or pred.shape != gt.shape:
+        raise RuntimeError(f"surface_metrics: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must be equal [N,(K,)H,W]")
+    for t, name in ((pred, "pred"), (gt, "gt")):
+        if t.dtype not in (torch.float32, torch.int64) or not t.is_cuda:
+            raise RuntimeError(f"surface_metrics: {name} must be a float32 or int64 HIP tensor, got {t.dtype} on {t.device}")
+    K = n_classes if by_class else (pred.shape[1] if pred.dim() == 4 else 1)
+    nb = lib.ustrun_surface_metrics_work_bytes(N, K, H, W)
+    if nb < 0:
+        L.check(1, "ustrun_surface_metrics_work_bytes")
+    work = torch.empty(nb, dtype=torch.uint8, device=pred.device)
+    out = torch.empty((N, K, SURFACE_RECORD_I32), dtype=torch.int32, device=pred.device)
+    L.check(lib.ustrun_surface_metrics(pred.data_ptr(), gt.data_ptr(), int(pred.dtype == torch.int64),
+                                       int(gt.dtype == torch.int64), N, K, int(by_class), H, W, work.data_ptr(), nb,
+                                       out.data_ptr(), stream_ptr()), "ustrun_surface_metrics")
+    return out
+
+
 def sgd_ema(p, g, v, t, lr, momentum, weight_decay, first, alpha, grad_scale=1.0):
     """Fused SGD(momentum, wd) step on flat f32 buffers + EMA teacher update (train.py:512,848,87-93)."""
     lib = L.lib()

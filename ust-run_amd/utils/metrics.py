@@ -4,6 +4,11 @@
 overlap counts can also come from the device (ustrun.functional.dice_counts): `dice_from_counts`
 applies the same formula to them, so the training step needs one small D2H copy instead of moving
 whole masks to the host.
+
+`surface_from_records` is the host part of the medpy metrics the reference's test() prints beside the Dice
+(binary.dc / jc / hd95 / asd, train.py:306-325): the device (ustrun.functional.surface_metrics) delivers, per sample and
+part, the border sizes, the two integer order statistics of the squared surface distances and the sum of the
+prediction's distances; the square roots, numpy's linear percentile and the reference's empty-mask rules are applied here.
 """
 import numpy as np
 
@@ -19,6 +24,48 @@ def dice_from_counts(s, g, i):
     s, g, i = np.asarray(s, dtype=np.float64), np.asarray(g, dtype=np.float64), np.asarray(i, dtype=np.float64)
     d = (2.0 * i + 1.0) / (1.001 + s + g)
     return np.where((s == 0) & (g == 0), 0.0, d)
+
+
+EMPTY_PRED_VALUE = 100.0          # train.py:313-315: hd and asd of a sample whose prediction is empty
+
+
+class EmptyGroundTruth(RuntimeError):
+    """hd95 / asd asked for a (sample, part) whose ground truth is empty; `.sample`, `.part` index the arrays given."""
+
+    def __init__(self, sample, part, where=""):
+        super().__init__(f"surface metrics: {where}sample {sample}, part {part}: the ground truth is empty "
+                         "(hd95 / asd are undefined; the reference's medpy raises here)")
+        self.sample, self.part = int(sample), int(part)
+
+
+def surface_from_records(records, counts, where=""):
+    """records: int32 [N, parts, 6] of ustrun.functional.surface_metrics; counts: [N, parts, 3] = {|P|, |G|, |P & G|}
+    (dice_counts).  -> (dc, jc, hd95, asd), float64 [N, parts] each:
+      dc = 2|P&G| / (|P|+|G|), 0.0 on 0/0;  jc = |P&G| / |P|G|;
+      hd95 = numpy.percentile(both directions' distances, 95): linear between sqrt(d2[k]) and sqrt(d2[k+1]) at 0.95 (n-1);
+      asd = sum of the prediction's distances / |border(P)|;  |P| = 0 -> hd95 = asd = 100;
+      |G| = 0 -> EmptyGroundTruth, a RuntimeError (medpy raises on an empty reference object), naming `where` (the caller's
+      words for the batch), the sample and the part."""
+    rec = np.ascontiguousarray(_np(records), dtype=np.int32)
+    cnt = np.asarray(_np(counts), dtype=np.int64)
+    if rec.ndim != 3 or rec.shape[2] != 6 or cnt.shape != rec.shape[:2] + (3,):
+        raise ValueError(f"surface_from_records: records {rec.shape} / counts {cnt.shape} are not [N,parts,6] / [N,parts,3]")
+    s, g, i = cnt[..., 0], cnt[..., 1], cnt[..., 2]
+    if (g == 0).any():
+        raise EmptyGroundTruth(*np.argwhere(g == 0)[0], where)
+    dc = np.where(s + g > 0, 2.0 * i / np.maximum(s + g, 1), 0.0)
+    jc = i / (s + g - i).astype(np.float64)
+    nbp, nbg = rec[..., 0].astype(np.int64), rec[..., 1].astype(np.int64)
+    total = np.ascontiguousarray(rec[..., 4:6]).view(np.float64)[..., 0]
+    n = nbp + nbg
+    pos = 0.95 * (n - 1).astype(np.float64)
+    t = pos - np.floor(pos)
+    a, b = np.sqrt(rec[..., 2].astype(np.float64)), np.sqrt(rec[..., 3].astype(np.float64))
+    # numpy's _lerp: a + (b-a) t, and b - (b-a)(1-t) from t = 0.5 on
+    hd = np.where(t >= 0.5, b - (b - a) * (1 - t), a + (b - a) * t)
+    asd = total / np.maximum(nbp, 1)
+    empty = s == 0
+    return dc, jc, np.where(empty, EMPTY_PRED_VALUE, hd), np.where(empty, EMPTY_PRED_VALUE, asd)
 
 
 def dice_coefficient_numpy(binary_segmentation, binary_gt_label):
