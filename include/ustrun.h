@@ -384,6 +384,10 @@ int ustrun_unet_backward_part(const ustrun_unet_desc_t* d, const float* x, const
  * w_fwd holds ustrun_pack_conv_elems() elements of the compute dtype                                                      */
 int ustrun_pack_conv(const float* w, int Cout, int Cin, int taps, void* w_fwd, int dtype, ustrun_stream_t s);
 int64_t ustrun_pack_conv_elems(int Cout, int Cin, int taps);
+/* the same count for a given compute dtype: ustrun_pack_conv_elems() for USTRUN_F32 / BF16 / F16; USTRUN_F32X3 packs the f32
+ * slices and then, when Cin % 8 == 0, their three bf16 planes [tap][plane][Cin/8][Cout][8] behind them (what the three-term implicit
+ * GEMM reads) -- 2.5 x the floats.  A buffer handed to ustrun_pack_conv with USTRUN_F32X3 must be sized with this entry.       */
+int64_t ustrun_pack_conv_elems_dtype(int Cout, int Cin, int taps, int dtype);
 /* k x k convolution (k = 1, 3, 5, 7), stride 1 or 2, dilation d, padding d * (k / 2) (nn.Conv2d of resnet.py:8-15,124 and
  * deeplabv2.py:15-17) of the concatenated sources -> y [N, Ho, Wo, Cout] (compute dtype, or f32 when y_f32); bias optional;
  * stat (optional): BatchNorm-statistics partial rows [rows][2][Cout] -- the buffer must hold ustrun_conv_mtiles(N, Ho, Wo,
@@ -481,7 +485,9 @@ int ustrun_debug_last_conv_variant(void);
  * Same for the last weight-gradient launch: the one-tap-per-block kernel (wgrad_tap_bf16.hip) reports
  * 0x54000000 | (TM / 64) << 20 | (TN / 64) << 16 | loader << 12 | ksplit (loader 2 = pixel-linear 1x1, 1 = one shifted tap,
  * 0 = k x k taps); the all-taps halo kernel 0x48000000 | build << 20 | ksplit (build 0 = round-2 kernel, 1 = buffer-addressed
- * transfers, 2 = two wave groups in opposite phases); 0 before any / for the generic kernels.
+ * transfers, 2 = two wave groups in opposite phases); dtype USTRUN_F32X3's one-tap-per-block kernel (wgrad_tap_x3.hip)
+ * 0x58000000 | (TM / 64) << 20 | (TN / 64) << 16 | slab layout << 12 | ksplit (layout 1 = one tap, slabs [Cout][Cin]; 0 = 3 x 3 taps,
+ * slabs [tap][Cin][Cout]); 0 before any / for the generic kernels.
  * ustrun_debug_last_conv_variant of the ConvTranspose / 1x1 GEMM kernel: 0x43540000 | (weights through registers ? 0x1000 : 0) |
  * (BN / 32) << 8 | (BK / 32) << 4 | mode (0 forward, 1 input gradient, 2 plain 1x1)                              */
 int ustrun_debug_last_wgrad_variant(void);

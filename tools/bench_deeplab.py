@@ -20,7 +20,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=16)
     ap.add_argument("--hw", type=int, default=512)
-    ap.add_argument("--dtype", default="bf16")
+    ap.add_argument("--dtype", default="bf16", choices=["f32", "f32x3", "bf16", "f16"],
+                    help="f32x3: f32 tensors, products as three-term bf16 splits (the U-Net's --amp 0 arithmetic)")
     ap.add_argument("--mode", default="train")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--arch", default="resnet101")

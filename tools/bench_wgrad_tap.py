@@ -3,7 +3,9 @@
 ustrun_conv2d_wgrad, one at a time: ms and TFLOP/s per shape, weighted by how often the network runs it.  Development tool; under
 rocprofv3 --pmc (tools/pmc_wgrad_tap.sh) with --only it gives the SQ counters of exactly one shape.
 
-    python3 tools/bench_wgrad_tap.py [--n 16] [--reps 5] [--only NAME] [--plain 0|1]
+    python3 tools/bench_wgrad_tap.py [--n 16] [--reps 5] [--only NAME] [--plain 0|1] [--dtype bf16|f32|f32x3]
+
+--dtype f32 against --dtype f32x3 is the A/B of the three-term one-tap kernel (wgrad_tap_x3.hip) against the generic f32 kernel.
 """
 import argparse
 import ctypes as C
@@ -41,9 +43,11 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only", default="")
     ap.add_argument("--plain", type=int, default=0, help="1: the source is a finished activation (no BatchNorm + ReLU on load)")
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "f32x3"])
     a = ap.parse_args()
     lib = l.lib()
-    bf = torch.bfloat16
+    dt = {"bf16": l.BF16, "f32": l.F32, "f32x3": l.F32X3}[a.dtype]
+    bf = torch.bfloat16 if dt == l.BF16 else torch.float32
     tot_ms = tot_fl = 0.0
     print(f"{'shape':28s} {'GF':>7s} {'ms':>7s} {'TF/s':>6s} {'x':>3s}  variant")
     for name, ci, co, k, d, hw, cnt in SHAPES:
@@ -57,7 +61,7 @@ def main():
         part = torch.empty(pb // 4, device="cuda")
         dw = torch.empty(co, ci, k, k, device="cuda")
         fn = lambda: l.check(lib.ustrun_conv2d_wgrad(C.byref(src), 1, dy.data_ptr(), a.n, hw, hw, co, k, 1, d, dw.data_ptr(), 0, part.data_ptr(),
-                                                     pb, 1, None), "wgrad")
+                                                     pb, dt, None), "wgrad")
         ms = timed(fn, a.reps)
         fl = 2.0 * a.n * hw * hw * ci * co * k * k
         print(f"{name:28s} {fl / 1e9:7.1f} {ms:7.3f} {fl / ms / 1e9:6.0f} {cnt:3d}  {lib.ustrun_debug_last_wgrad_variant():#x}", flush=True)

@@ -412,6 +412,10 @@ extern "C" int64_t ustrun_wgrad_partials_bytes(int nseg, int Cin, int Cout, int6
         int kt; long ct;
         wgrad_tap_plan(t, &kt, &ct);
         if (kt > slabs) slabs = kt;
+        if (nseg == 1 || nseg == 9) {                             // dtype USTRUN_F32X3's one-tap kernel: 32-pixel stages, may split further
+            wgrad_tap_x3_plan(t, &kt, &ct);
+            if (kt > slabs) slabs = kt;
+        }
     }
     if (nseg == 4 && Cin % 64 == 0 && Cout % 64 == 0) {          // dtype USTRUN_F32X3's ConvTranspose kernel: at most one block per CU and pair
         const long pairs = (long)(Cin / 64) * (Cout / 64);

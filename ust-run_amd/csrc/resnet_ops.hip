@@ -307,11 +307,19 @@ extern "C" int ustrun_pack_conv(const float* w, int Cout, int Cin, int taps, voi
     hipLaunchKernelGGL(pack_conv_f32_kernel, dim3(stream_blocks((long)Cout * Cin * taps)), dim3(256), 0, (hipStream_t)s, w, Cout, Cin,
                        taps, (float*)w_fwd);
     USTRUN_LAUNCH_CHECK("pack_conv");
+    // the three bf16 planes behind the f32 pack, [slice][plane][Cin/8][Cout][8] (x3.hip; none when Cin % 8: no x3 kernel takes such a layer)
+    if (dtype == USTRUN_F32X3) USTRUN_TRY(pack_x3((const float*)w_fwd, taps, Cin, Cout, (hipStream_t)s));
     return 0;
 }
 
 extern "C" int64_t ustrun_pack_conv_elems(int Cout, int Cin, int taps) {
     return (int64_t)taps * ((Cin + 7) / 8 * 8) * ((Cout + 7) / 8 * 8);
+}
+
+// USTRUN_F32X3: the f32 pack (taps * Cin * Cout floats) and 3 planes of as many bf16 values behind it -- 2.5 x the floats
+extern "C" int64_t ustrun_pack_conv_elems_dtype(int Cout, int Cin, int taps, int dtype) {
+    const int64_t e = ustrun_pack_conv_elems(Cout, Cin, taps);
+    return dtype == USTRUN_F32X3 ? (5 * e + 1) / 2 : e;
 }
 
 extern "C" int ustrun_conv2d_fwd(const ustrun_src_t* srcs, int nsrc, const void* w_fwd, const float* bias, int N, int Ho, int Wo,
@@ -626,6 +634,29 @@ extern "C" int ustrun_conv2d_wgrad(const ustrun_src_t* srcs, int nsrc, const voi
         double in_elems = (double)N * srcs[0].H * srcs[0].W * srcs[0].C;
         prof_begin(1, 2.0 * a.M * a.nseg * a.Cin * Cout, 2.0 * (in_elems + (double)a.M * Cout) + 4.0 * a.nseg * a.Cin * Cout, (hipStream_t)s);
         const int rc = wgrad_tap_launch_bf16(a, (hipStream_t)s);
+        prof_end((hipStream_t)s);
+        USTRUN_TRY(rc);
+        // 1x1: the slabs are [Cout][Cin] = the torch layout already (plain streaming sum); k x k: [tap][Cin][Cout] -> transposed
+        return reduce_partials(partials, a.ksplit, a.nseg, a.Cin, Cout, dw, a.nseg == 1 ? 2 : 0, accumulate, (hipStream_t)s);
+    }
+    // dtype USTRUN_F32X3 (three-term bf16 products): the all-taps kernel for the plain 3x3, the one-tap-per-block kernel for the 1x1 /
+    // strided / dilated layers, the f32 matrix-core kernel for everything else (channel counts that are no multiple of 64)
+    if (dtype == USTRUN_F32X3 && wgrad_x3_supported(a)) {
+        int per;
+        wgrad_x3_plan(a, &slabs, &per);
+        USTRUN_CHECK(partials_bytes >= (int64_t)slabs * 9 * a.Cin * Cout * 4, "conv2d_wgrad: partials too small");
+        prof_begin(1, 2.0 * a.M * 9 * a.Cin * Cout, 4.0 * ((double)a.M * a.Cin + (double)a.M * Cout) + 36.0 * a.Cin * Cout, (hipStream_t)s);
+        const int rc = wgrad_x3_launch(a, slabs, per, (hipStream_t)s);
+        prof_end((hipStream_t)s);
+        USTRUN_TRY(rc);
+        return reduce_partials(partials, slabs, 9, a.Cin, Cout, dw, 2, accumulate, (hipStream_t)s);   // slabs are in torch layout
+    }
+    if (dtype == USTRUN_F32X3 && wgrad_tap_x3_supported(a)) {
+        wgrad_tap_x3_plan(a, &a.ksplit, &a.kchunk);
+        USTRUN_CHECK(partials_bytes >= (int64_t)a.ksplit * a.nseg * a.Cin * Cout * 4, "conv2d_wgrad: partials too small");
+        double in_elems = (double)N * srcs[0].H * srcs[0].W * srcs[0].C;
+        prof_begin(1, 2.0 * a.M * a.nseg * a.Cin * Cout, 4.0 * (in_elems + (double)a.M * Cout) + 4.0 * a.nseg * a.Cin * Cout, (hipStream_t)s);
+        const int rc = wgrad_tap_x3_launch(a, (hipStream_t)s);
         prof_end((hipStream_t)s);
         USTRUN_TRY(rc);
         // 1x1: the slabs are [Cout][Cin] = the torch layout already (plain streaming sum); k x k: [tap][Cin][Cout] -> transposed

@@ -1,0 +1,290 @@
+// wgrad_tap_x3.hip -- dtype USTRUN_F32X3: weight gradient of a 1x1 / dilated / strided k x k convolution (k = 1, 3) with three-term
+// bf16 products, one TAP per block (the DeepLabV2-ResNet bottlenecks, projection shortcuts, stem patches and classifier GEMM: every
+// weight gradient the all-taps kernel of x3.hip -- undilated stride-1 3x3 only -- does not take):
+//
+//   dW[tap][ci][co] = sum_p act(x[stride * p + dilation * (tap - k/2)][ci]) * dy[p][co]          p over the output grid
+//
+// The tiling and the WgradArgs contract are wgrad_tap_bf16.hip's: a block owns TM (128 or 64) ci x TN (128 or 64) co of one tap and a
+// contiguous range of output pixels (split-K over space), waves 2 x 2, partial slabs summed in a fixed order by reduce_partials.
+// The arithmetic is wgrad_x3_kernel's: both operands are f32 NHWC in HBM; a staged value goes global -> registers -> [BatchNorm
+// affine + ReLU in f32, zero outside the image / the pixel range] -> split4 -> three bf16 planes in LDS, [plane][pixel][channel]
+// with that kernel's row pitch and XOR of the 64-byte segments, so the K-major MFMA fragments (K = the pixel) come from the
+// transposing LDS read; a fragment pair is six MFMAs, smallest terms first, term by term over the wave's accumulators.
+//
+// Stage = 32 pixels: LDS 3 planes x 32 x (TM + TN) x 2 B = 48 KB for the 128 x 128 tile, one buffer -- the loads of stage s + 1 are
+// issued before the MFMAs of stage s and split into LDS after them; two blocks per CU (96 of 160 KB) cover each other's splits and
+// barriers.  Per stage and wave (128 x 128): 48 MFMAs (1536 matrix-pipe cycles) against 24 transposing reads and ~320 VALU
+// instructions of splitting per lane.
+#include "common.h"
+#include "loader.h"
+#include "x3_split.h"
+
+namespace ustrun {
+namespace {
+
+constexpr int KP = 32;   // pixels per stage
+
+// as wgrad_tap_bf16.hip: the 64-byte segments of a row are XOR-permuted by the row index so that the 4 rows of a transposed read
+// fall on different bank segments (256-byte rows: row & 3; 128-byte rows: (row >> 1) & 1)
+template <int RB> __device__ __forceinline__ int seg_swz(int row) { return RB >= 256 ? (row & 3) : ((row >> 1) & 1); }
+
+// rows k0 + 8*(l>>5) + {0..3 | 4..7}, columns col0 + 16*((l>>4)&1) + 4*(l&3) .. +3, delivered column-major
+template <int RB> __device__ __forceinline__ b16x8 tr_frag(const char* tile, int k0, int col0, int lane) {
+    const int q = (lane & 15) >> 2, p = lane & 3;
+    const int colb = (col0 + 16 * ((lane >> 4) & 1) + 4 * p) * 2;
+    const int r0 = k0 + 8 * (lane >> 5) + q, r1 = r0 + 4;
+    const b16x4 lo = __builtin_bit_cast(b16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((ustrun_lds_s16x4*)(tile + r0 * RB + (colb ^ (seg_swz<RB>(r0) << 6)))));
+    const b16x4 hi = __builtin_bit_cast(b16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((ustrun_lds_s16x4*)(tile + r1 * RB + (colb ^ (seg_swz<RB>(r1) << 6)))));
+    b16x8 f;
+    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
+    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
+    return f;
+}
+
+// v / d and the remainder for 0 <= v < 2^24 through the float reciprocal (two fix-up steps make it exact)
+__device__ __forceinline__ int fdiv(int v, int d, float invd, int& rem) {
+    int q = (int)(((float)v + 0.5f) * invd);
+    int r = v - q * d;
+    if (r < 0) { --q; r += d; }
+    if (r >= d) { ++q; r -= d; }
+    rem = r;
+    return q;
+}
+
+// grid = (ci tiles * co tiles * taps * ksplit)
+// SWAP (1x1 convolutions): the MFMA operands trade places, D rows are co and its lanes ci, so the slab comes out as [co][ci] --
+// the torch layout of a 1x1 weight -- and the fixed-order streaming sum finishes it without a transposing pass.
+template <int TM, int TN, bool SWAP>
+__global__ __launch_bounds__(256, 2) void wgrad_tap_x3_kernel(const WgradArgs a, const int mtn, const int ntn) {
+    constexpr int RBA = TM * 2, RBB = TN * 2;                 // LDS row pitches (bytes)
+    constexpr int APLANE = KP * RBA, BPLANE = KP * RBB;       // one plane of a tile
+    constexpr int AQ = TM / 4, AROWS = 256 / AQ, AP = KP / AROWS;      // 16-byte (4 x f32) items per row, rows per pass, passes
+    constexpr int BQ = TN / 4, BROWS = 256 / BQ, BP = KP / BROWS;
+    constexpr int MI = TM / 64, NI = TN / 64;                 // 32 x 32 MFMA tiles per wave (waves 2 x 2)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* As = smem;                      // [3][KP][TM] bf16
+    char* Bs = smem + 3 * APLANE;         // [3][KP][TN] bf16
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    // XCD-aware order (1-D grid, workgroups go round-robin over the 8 XCDs): every XCD takes a contiguous range of the
+    // (slice-major, tile-minor) order, so all (tap, ci, co) tiles of one pixel slice share one XCD's L2
+    const int nblk = gridDim.x, tiles = nblk / a.ksplit;
+    int lin;
+    {
+        const int q = nblk / 8, r = nblk % 8, xcd = blockIdx.x % 8, jj = blockIdx.x / 8;
+        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + jj;
+    }
+    const int ks = lin / tiles;
+    int tile = lin - ks * tiles;
+    const int ntile = tile % ntn; tile /= ntn;
+    const int mtile = tile % mtn;
+    const int seg = tile / mtn;
+    const int ci0 = mtile * TM, co0 = ntile * TN;
+    const int ady = a.d0 + (seg / a.segw) * a.astep, adx = a.d0 + (seg % a.segw) * a.astep;
+    const int kbeg = (int)((long)ks * a.kchunk);
+    const int kend = (kbeg + a.kchunk < a.M) ? (int)(kbeg + a.kchunk) : (int)a.M;
+    const int Wb = a.Wb, Hb = a.Hb;
+    const float invW = 1.f / (float)Wb, invH = 1.f / (float)Hb;
+
+    // ---- activation items: pixel row tid / AQ + AROWS i of the stage, 4-channel group tid % AQ ----
+    const SrcDev& S = a.src[0];
+    const int c4 = tid % AQ, arow = tid / AQ;
+    const int cl = ci0 + 4 * c4;
+    f32x4 asc = {1.f, 1.f, 1.f, 1.f}, ash = {0.f, 0.f, 0.f, 0.f};
+    if (S.scale) { asc = *(const f32x4*)(S.scale + cl); ash = *(const f32x4*)(S.shift + cl); }
+    const float floor_ = S.relu ? 0.f : -__builtin_inff();
+    const float* sp = S.ptr + cl;
+    const int sN = (int)S.sN, sH = (int)S.sH, sW = (int)S.sW;        // element offsets fit 31 bits (host check)
+    f32x4 av[AP];
+    unsigned aok = 0;
+    // every load is issued unconditionally from an in-range address (the source's first pixel for rows outside the pixel range /
+    // the image) and the row is zeroed at the split: no load is ever addressed outside the tensor
+    auto load_A = [&](int k0) {
+        aok = 0;
+#pragma unroll
+        for (int i = 0; i < AP; ++i) {
+            const int m = k0 + arow + AROWS * i;
+            int px, py;
+            const int r = fdiv(m < kend ? m : kbeg, Wb, invW, px);
+            const int pn = fdiv(r, Hb, invH, py);
+            const int ly = (py << a.ashift) + ady - S.off_y, lx = (px << a.ashift) + adx - S.off_x;
+            const int ok = (int)(m < kend) & (int)((unsigned)ly < (unsigned)S.LH) & (int)((unsigned)lx < (unsigned)S.LW);
+            const int off = pn * sN + ly * sH + lx * sW;
+            av[i] = *(const f32x4*)(sp + (ok ? off : 0));
+            aok |= (unsigned)ok << i;
+        }
+    };
+    auto write_A = [&]() {
+#pragma unroll
+        for (int i = 0; i < AP; ++i) {
+            const int row = arow + AROWS * i;
+            f32x4 v = av[i] * asc + ash;                     // BatchNorm affine + ReLU in f32, before the split
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = __builtin_fmaxf(v[q], floor_);
+            if (!((aok >> i) & 1u)) v = (f32x4){0.f, 0.f, 0.f, 0.f};       // padding / the range's tail, applied after the activation
+            u32x2 p0, p1, p2;
+            split4(v, p0, p1, p2);
+            char* dst = As + row * RBA + ((c4 * 8) ^ (seg_swz<RBA>(row) << 6));
+            *(u32x2*)dst = p0; *(u32x2*)(dst + APLANE) = p1; *(u32x2*)(dst + 2 * APLANE) = p2;
+        }
+    };
+    // ---- dy items: the same (row, 4-channel group) pattern over pixel-linear rows of Cout floats ----
+    const int b4 = tid % BQ, brow = tid / BQ;
+    const float* dyp = a.dy + co0 + 4 * b4;
+    const int dyC = a.Cout;
+    f32x4 bv[BP];
+    auto load_B = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < BP; ++i) {
+            const int m = k0 + brow + BROWS * i;
+            bv[i] = *(const f32x4*)(dyp + (m < kend ? m : kbeg) * dyC);      // (rows past the range: an in-range pixel, zeroed below)
+        }
+    };
+    auto write_B = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < BP; ++i) {
+            const int row = brow + BROWS * i;
+            const f32x4 v = (k0 + row < kend) ? bv[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
+            u32x2 p0, p1, p2;
+            split4(v, p0, p1, p2);
+            char* dst = Bs + row * RBB + ((b4 * 8) ^ (seg_swz<RBB>(row) << 6));
+            *(u32x2*)dst = p0; *(u32x2*)(dst + BPLANE) = p1; *(u32x2*)(dst + 2 * BPLANE) = p2;
+        }
+    };
+
+    f32x16 acc[MI][NI];
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < NI; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    if (kbeg < kend) {
+        load_A(kbeg);
+        load_B(kbeg);
+        write_A();
+        write_B(kbeg);
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int k0 = kbeg; k0 < kend; k0 += KP) {
+        const bool more = k0 + KP < kend;
+        if (more) {                                   // in flight under this stage's MFMAs
+            load_A(k0 + KP);
+            load_B(k0 + KP);
+        }
+#pragma unroll
+        for (int kk = 0; kk < KP / 16; ++kk) {
+            b16x8 af[MI][3], bf[NI][3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+#pragma unroll
+                for (int i = 0; i < MI; ++i) af[i][p] = tr_frag<RBA>(As + p * APLANE, kk * 16, wm * (TM / 2) + 32 * i, lane);
+#pragma unroll
+                for (int j = 0; j < NI; ++j) bf[j][p] = tr_frag<RBB>(Bs + p * BPLANE, kk * 16, wn * (TN / 2) + 32 * j, lane);
+            }
+            // mfma6's order (small terms first), term by term over the wave's accumulators: the six products of one accumulator
+            // stand MI * NI instructions apart instead of back to back
+            constexpr int TA[6] = {0, 1, 2, 0, 1, 0}, TB[6] = {2, 1, 0, 1, 0, 0};
+#pragma unroll
+            for (int q = 0; q < 6; ++q)
+#pragma unroll
+                for (int i = 0; i < MI; ++i)
+#pragma unroll
+                    for (int j = 0; j < NI; ++j)
+                        acc[i][j] = SWAP ? X3_MFMA(bf[j][TB[q]], af[i][TA[q]], acc[i][j], 0, 0, 0)
+                                         : X3_MFMA(af[i][TA[q]], bf[j][TB[q]], acc[i][j], 0, 0, 0);
+        }
+        __syncthreads();                              // every wave is done reading this stage
+        if (more) {
+            write_A();
+            write_B(k0 + KP);
+        }
+        __syncthreads();
+    }
+
+    float* slab = a.partials + ((long)ks * a.nseg + seg) * a.Cin * a.Cout;
+    const int l31 = lane & 31, lh = lane >> 5;
+    if (SWAP) {
+        // slab [ks][Cout][Cin]: rows of D are co (registers), the 32 lanes of a row are consecutive ci
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+            const int ci = ci0 + wm * (TM / 2) + i * 32 + l31;
+#pragma unroll
+            for (int j = 0; j < NI; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int co = co0 + wn * (TN / 2) + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    slab[(long)co * a.Cin + ci] = acc[i][j][r];
+                }
+        }
+    } else {
+        // slab [ks][tap][Cin][Cout]: rows of D are ci (registers), the 32 lanes of a row are consecutive co
+#pragma unroll
+        for (int j = 0; j < NI; ++j) {
+            const int co = co0 + wn * (TN / 2) + j * 32 + l31;
+#pragma unroll
+            for (int i = 0; i < MI; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int ci = ci0 + wm * (TM / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    slab[(long)ci * a.Cout + co] = acc[i][j][r];
+                }
+        }
+    }
+}
+
+int tile_m(const WgradArgs& a) { return a.Cin % 128 == 0 ? 128 : 64; }
+int tile_n(const WgradArgs& a) { return a.Cout % 128 == 0 ? 128 : 64; }
+
+template <int TM, int TN>
+int launch_tile(const WgradArgs& a, hipStream_t st) {
+    const int mtn = a.Cin / TM, ntn = a.Cout / TN;
+    dim3 grid(mtn * ntn * a.nseg * a.ksplit), block(256);
+    constexpr int lds = 3 * KP * (TM + TN) * 2;               // <= 48 KB
+    if (a.nseg == 1) hipLaunchKernelGGL((wgrad_tap_x3_kernel<TM, TN, true>), grid, block, lds, st, a, mtn, ntn);
+    else hipLaunchKernelGGL((wgrad_tap_x3_kernel<TM, TN, false>), grid, block, lds, st, a, mtn, ntn);
+    USTRUN_LAUNCH_CHECK("wgrad_tap_x3");
+    return 0;
+}
+
+}  // namespace
+
+bool wgrad_tap_x3_supported(const WgradArgs& a) {
+    if (g_debug_flags & (1 << 29)) return false;                   // (A/B runs against the f32 matrix-core kernel)
+    if (a.dy_s != 1 || a.dy_esz != 4 || a.nsrc != 1 || a.ashift < 0 || a.ashift > 1 || a.astep < 1) return false;
+    if (!((a.nseg == 1 && a.segw == 1) || (a.nseg == 9 && a.segw == 3))) return false;      // k = 1 or 3
+    const SrcDev& s = a.src[0];
+    if (s.esz != 4 || s.sC != 1 || s.pool || s.gN > 0 || s.C != a.Cin) return false;
+    if ((s.sW & 3) || (s.sH & 3) || (s.sN & 3)) return false;                 // 16-byte loads of 4 channels
+    if (a.dyH != a.Hb || a.dyW != a.Wb || a.M <= 0 || a.M >= (1L << 24)) return false;      // float-reciprocal pixel decomposition
+    if ((long)a.N * s.sN >= (1L << 31) - 64 || a.M * a.Cout >= (1L << 31) - 64) return false;      // 32-bit element offsets
+    return a.Cin % 64 == 0 && a.Cout % 64 == 0;
+}
+
+// split-K plan: at most one resident round of blocks (2 per CU), at least four 32-pixel stages per block
+int wgrad_tap_x3_plan(const WgradArgs& a, int* ksplit, long* kchunk) {
+    const long tiles = (long)(a.Cin / tile_m(a)) * (a.Cout / tile_n(a)) * a.nseg;
+    long ks = 512 / tiles;
+    if (ks > a.M / (4 * KP)) ks = a.M / (4 * KP);
+    if (ks < 1) ks = 1;
+    long chunk = (a.M + ks - 1) / ks;
+    chunk = (chunk + KP - 1) / KP * KP;
+    *kchunk = chunk; *ksplit = (int)((a.M + chunk - 1) / chunk);
+    return 0;
+}
+
+int wgrad_tap_x3_launch(const WgradArgs& a, hipStream_t st) {
+    const int tm = tile_m(a), tn = tile_n(a);
+    // 'X' | TM/64 | TN/64 | slab layout (1 = one tap, [co][ci]; 0 = k x k taps, [tap][ci][co]) | ksplit   (tests: ustrun_debug_last_wgrad_variant)
+    set_last_wgrad_variant(0x58000000 | (tm / 64) << 20 | (tn / 64) << 16 | (a.nseg == 1 ? 1 : 0) << 12 | (a.ksplit & 0xfff));
+    if (tm == 128 && tn == 128) return launch_tile<128, 128>(a, st);
+    if (tm == 128) return launch_tile<128, 64>(a, st);
+    if (tn == 128) return launch_tile<64, 128>(a, st);
+    return launch_tile<64, 64>(a, st);
+}
+
+}  // namespace ustrun

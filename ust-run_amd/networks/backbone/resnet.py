@@ -49,7 +49,7 @@ class ResNet(nn.Module):
         if len(dil) != 3:
             raise ValueError("replace_stride_with_dilation should be None "
                              "or a 3-element tuple, got {}".format(replace_stride_with_dilation))
-        self.compute_dtype = dtype
+        self.compute_dtype = dtype            # "f32" | "f32x3" | "bf16" | "f16" (ustrun.resnet_engine._DT)
         self.channels = [w * block.expansion for w in (64, 128, 256, 512)]
         self._norm_layer = norm_layer or nn.BatchNorm2d
         self.groups, self.base_width = groups, width_per_group

@@ -101,6 +101,7 @@ SIGNATURES = {
     "ustrun_amp_update": (i32, [fp, f32, f32, i32, vp]),
     "ustrun_pack_conv": (i32, [fp, i32, i32, i32, vp, i32, vp]),
     "ustrun_pack_conv_elems": (i64, [i32, i32, i32]),
+    "ustrun_pack_conv_elems_dtype": (i64, [i32, i32, i32, i32]),
     "ustrun_conv2d_fwd": (i32, [PSrc, i32, vp, fp, i32, i32, i32, i32, i32, i32, i32, vp, i32, fp, C.POINTER(C.c_int), i32, vp]),
     "ustrun_conv_rowwin_fwd": (i32, [PSrc, vp, i32, i32, i32, i32, i32, i32, vp, fp, C.POINTER(C.c_int), i32, vp]),
     "ustrun_maxpool3x3s2": (i32, [vp, fp, fp, i32, i32, i32, i32, vp, i32, vp]),

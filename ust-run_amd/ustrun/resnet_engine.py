@@ -24,7 +24,18 @@ import torch
 from . import _lib as L
 from .engine import stream_ptr
 
-_DT = {"f32": L.F32, "bf16": L.BF16, "f16": L.F16}
+_DT = {"f32": L.F32, "bf16": L.BF16, "f16": L.F16, "f32x3": L.F32X3}
+
+
+def _is16(dt):
+    """16-bit storage (bf16 / f16): the passes that re-lay or materialise 16-bit operands exist for these only -- "f32x3" keeps
+    f32 tensors and reads its operands through the loaders like "f32"."""
+    return dt in (L.BF16, L.F16)
+
+
+def _pack_buf(co, ci, taps, dt, dev):
+    """a zeroed buffer for ustrun_pack_conv (f32x3: the f32 pack and the three bf16 planes behind it)"""
+    return torch.zeros(L.lib().ustrun_pack_conv_elems_dtype(co, ci, taps, dt), dtype=_tdtype(dt), device=dev)
 
 
 class Act:
@@ -63,8 +74,7 @@ def _packed(conv, dt):
     if getattr(conv, "_ustrun_pack_key", None) != key:
         lib = L.lib()
         co, ci, kh, kw = conv.weight.shape
-        n = lib.ustrun_pack_conv_elems(co, ci, kh * kw)
-        buf = torch.zeros(n, dtype=_tdtype(dt), device=conv.weight.device)
+        buf = _pack_buf(co, ci, kh * kw, dt, conv.weight.device)
         w = conv.weight.detach().contiguous()
         L.check(lib.ustrun_pack_conv(w.data_ptr(), co, ci, kh * kw, buf.data_ptr(), dt, stream_ptr()), "ustrun_pack_conv")
         conv._ustrun_pack, conv._ustrun_pack_key = buf, key
@@ -133,7 +143,7 @@ def stem(net, x, dt, train):
         w = conv.weight.detach().permute(0, 2, 3, 1).reshape(co, k, k * Cin)       # [co][ky][kx*Cin + ci]
         w = torch.nn.functional.pad(w, (0, win - k * Cin)).reshape(co, k * win)    # [co][ky*win + kx*Cin + ci]
         w = torch.nn.functional.pad(w, (0, Kp - k * win)).contiguous()             # zero weights meet the windows' overhang
-        buf = torch.zeros(lib.ustrun_pack_conv_elems(co, Kp, 1), dtype=_tdtype(dt), device=x.device)
+        buf = _pack_buf(co, Kp, 1, dt, x.device)
         L.check(lib.ustrun_pack_conv(w.data_ptr(), co, Kp, 1, buf.data_ptr(), dt, stream_ptr()), "ustrun_pack_conv")
         conv._ustrun_pack, conv._ustrun_pack_key = buf, key
     wsrc = L.Src(xp.data_ptr(), None, None, win, Hp, Wp - (win + Cin - 1) // Cin + 1, Hp * Wp * Cin, Wp * Cin, Cin, 1, 0, 0, 0, 0, 0, 0, 0)
@@ -227,8 +237,7 @@ def _classifier_gemm(net, dt):
         K, Cin = net.classifier[0].weight.shape[:2]
         wall = torch.stack([c.weight.detach().reshape(K, Cin, 9).permute(2, 0, 1) for c in net.classifier], 0)    # [r, tap, k, c]
         wall = wall.reshape(len(net.classifier) * 9 * K, Cin).contiguous()
-        n = lib.ustrun_pack_conv_elems(wall.shape[0], Cin, 1)
-        buf = torch.zeros(n, dtype=_tdtype(dt), device=wall.device)
+        buf = _pack_buf(wall.shape[0], Cin, 1, dt, wall.device)
         L.check(lib.ustrun_pack_conv(wall.data_ptr(), wall.shape[0], Cin, 1, buf.data_ptr(), dt, stream_ptr()), "ustrun_pack_conv")
         net._ustrun_cls = (buf, sum(c.bias.detach() for c in net.classifier).contiguous(), wall.shape[0])
         net._ustrun_cls_key = key
@@ -293,7 +302,7 @@ def _packed_dgrad(conv, dt):
         lib = L.lib()
         co, ci, kh, kw = conv.weight.shape
         wd = conv.weight.detach().flip(2, 3).transpose(0, 1).contiguous()
-        buf = torch.zeros(lib.ustrun_pack_conv_elems(ci, co, kh * kw), dtype=_tdtype(dt), device=wd.device)
+        buf = _pack_buf(ci, co, kh * kw, dt, wd.device)
         L.check(lib.ustrun_pack_conv(wd.data_ptr(), ci, co, kh * kw, buf.data_ptr(), dt, stream_ptr()), "ustrun_pack_conv")
         conv._ustrun_dpack, conv._ustrun_dpack_key = buf, key
     return conv._ustrun_dpack
@@ -358,7 +367,7 @@ def _conv_wgrad_here(x, dy, y, conv, grads, dt):
     part = _scratch.get("wgrad", pb, dy.device)
     dw = torch.empty_like(conv.weight)
     src = x.src()
-    if k == 3 and d > 1 and s == 1 and dt != L.F32 and _SPACE_TO_BATCH_WGRAD and ci % 64 == 0 and co % 64 == 0:
+    if k == 3 and d > 1 and s == 1 and _is16(dt) and _SPACE_TO_BATCH_WGRAD and ci % 64 == 0 and co % 64 == 0:
         # dilated 3x3: both operands re-laid as d x d sub-grid images (zero-padded to one extent; the activation pass does the
         # re-laying, so only dy costs a pass of its own) -> an ORDINARY 3x3 weight gradient over N d d images on the all-taps kernel
         Hs, Ws = -(-x.H // d), -(-x.W // d)
@@ -375,7 +384,7 @@ def _conv_wgrad_here(x, dy, y, conv, grads, dt):
                                         stream_ptr()), "ustrun_conv2d_wgrad")
         grads[conv.weight] = dw
         return
-    if x.aff is not None and dt != L.F32 and _MATERIALISE_WGRAD_OPERAND:
+    if x.aff is not None and _is16(dt) and _MATERIALISE_WGRAD_OPERAND:
         # the operand relu(bn(x)) written out once (4 B per element at the HBM rate) instead of being formed per staged item in
         # every one of the Cout / 128 column tiles and k * k taps of the weight gradient (2-18 times over: round 6)
         act = _scratch.get("wgrad_act", x.t.numel() * 2, dy.device)
@@ -451,7 +460,7 @@ def _conv3_dgrad_bn2(dy3, y3, y2, conv, bn, dt, grads):
     gradient's epilogue where the library covers the shape (one launch instead of the gradient + a reduce pass over da2 and y2)"""
     lib = L.lib()
     co, ci, k, _ = conv.weight.shape
-    if k == 1 and conv.stride[0] == 1 and dt != L.F32:
+    if k == 1 and conv.stride[0] == 1 and _is16(dt):
         da2 = torch.empty_like(y2.t)
         rows, fused = C.c_int(0), C.c_int(0)
         stat = _scratch.get("join_stat", lib.ustrun_conv_mtiles(y2.N, y2.H, y2.W, ci) * 2 * ci * 4, dy3.device)
@@ -469,7 +478,7 @@ def _conv2_dgrad_bn1(dy2, y2, y1, conv, bn, dt, grads):
     epilogue where the library covers the shape (stride 1, 16-bit storage, >= 128 channels)"""
     lib = L.lib()
     co, ci, k, _ = conv.weight.shape
-    if k == 3 and conv.stride[0] == 1 and dt != L.F32:
+    if k == 3 and conv.stride[0] == 1 and _is16(dt):
         da1 = torch.empty_like(y1.t)
         rows = C.c_int(0)
         stat = _scratch.get("join_stat", lib.ustrun_conv_mtiles(y1.N, y1.H, y1.W, ci) * 2 * ci * 4, dy2.device)
@@ -489,7 +498,7 @@ def _conv1_dgrad_join(dy1, y1, x, conv, dxb, ref, prev, dt, grads):
     -> (G_prev, coef of prev.bn3 or None)."""
     lib = L.lib()
     co, ci, k, _ = conv.weight.shape
-    if k == 1 and conv.stride[0] == 1 and dt != L.F32:
+    if k == 1 and conv.stride[0] == 1 and _is16(dt):
         dev = dy1.device
         g = torch.empty_like(x.t)
         y3p, bn3p = (prev[5], prev[1].bn3) if prev is not None else (None, None)
@@ -563,7 +572,7 @@ def _head_backward(rec, dlogits, dt, grads):
     if getattr(net, "_ustrun_clsd_key", None) != key:
         wall = torch.stack([c.weight.detach().reshape(K, Cin, 9).permute(2, 0, 1) for c in net.classifier], 0).reshape(ZC, Cin)
         wd = torch.nn.functional.pad(wall.t(), (0, ZCp - ZC)).contiguous()                          # [Cin][ZCp]
-        buf = torch.zeros(lib.ustrun_pack_conv_elems(Cin, ZCp, 1), dtype=_tdtype(dt), device=dev)
+        buf = _pack_buf(Cin, ZCp, 1, dt, dev)
         L.check(lib.ustrun_pack_conv(wd.data_ptr(), Cin, ZCp, 1, buf.data_ptr(), dt, stream_ptr()), "ustrun_pack_conv")
         net._ustrun_clsd, net._ustrun_clsd_key = buf, key
     dc4 = torch.empty_like(c4.t)
