@@ -123,6 +123,13 @@ int ustrun_maxpool_bwd(const void* dp, const void* x, int N, int H, int W, int C
 int ustrun_convT2x2_fwd(const ustrun_src_t* src, const void* w_fwd, const float* bias, int N, int H,
                         int W, int Cout, void* u, int dtype, ustrun_stream_t s);
 
+/* ---- input gradient of the first convolution (Conv2d(C, base, 3, padding=1, bias=False), unet_parts.py:16) ----
+ * dx[N,Cin,H,W] NCHW f32 (overwritten) from dy[N,H,W,Cout] in the storage dtype and the f32 PARAMETER w[Cout,Cin,3,3].
+ * Cin 1..4, Cout a multiple of 8 up to 64, any H, W >= 1.  Products of the stored values, f32 accumulation in a fixed
+ * order (bit-identical repeats); USTRUN_F32X3 runs the f32 build.                                                     */
+int ustrun_conv_first_dgrad(const void* dy, const float* w, int N, int H, int W, int Cout, int Cin, float* dx,
+                            int dtype, ustrun_stream_t s);
+
 /* ---- 1x1 head with bias: replaces OutConv, unet_parts.py:71-76 -----------------------------
  * logits NCHW f32 [N,K,H,W] from y[N,H,W,C] through the loader affine (scale/shift/relu).    */
 int ustrun_head_fwd(const void* y, const float* scale, const float* shift, int64_t npix, int HW,
@@ -377,6 +384,19 @@ int ustrun_unet_backward(const ustrun_unet_desc_t* d, const float* x, const floa
 int ustrun_unet_backward_part(const ustrun_unet_desc_t* d, const float* x, const float* dlogits,
                               void* workspace, void* scratch, float* const* grads, int accumulate, int part,
                               ustrun_stream_t s);
+/* ... with the two gradients that make both outputs of UNet.forward(x, feature=True) ordinary autograd tensors and the
+ * input a differentiable one (unet_model.py:25-39: `return logits, x_last64`; nothing there detaches x):
+ *   dfeat (optional) NCHW f32, the forward's feat layout: the gradient of the feature output.  It is added to the head's
+ *     input gradient in front of the last BatchNorm's backward; consumed by the part that runs the head (0 or 1).  The
+ *     leading passes' rows are ignored, as dlogits' are.  dlogits may be NULL when dfeat is given: it stands for zeros
+ *     (the head's weight and bias gradients are then zero).
+ *   dx (optional) NCHW f32 [N,C,H,W], overwritten: the gradient of the network input, ustrun_conv_first_dgrad of inc's
+ *     first convolution (unet_parts.py:16); written by the part that reaches layer 0 (0, 2 or 4).  Rows of leading
+ *     passes and of the tail pass are zero.  Needs C <= 4 and base a multiple of 8 up to 64.
+ * With dfeat == dx == NULL this IS ustrun_unet_backward_part, launch for launch.                                          */
+int ustrun_unet_backward_io(const ustrun_unet_desc_t* d, const float* x, const float* dlogits, const float* dfeat,
+                            void* workspace, void* scratch, float* const* grads, int accumulate, int part, float* dx,
+                            ustrun_stream_t s);
 
 /* ---- DeepLabV2-ResNet operators (reference networks/deeplabv2.py:10-33, networks/backbone/resnet.py:55-176; SURVEY.md 8f
  * row 4), forward and backward.  Activations NHWC in the compute dtype like the U-Net's.                                   */

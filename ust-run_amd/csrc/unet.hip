@@ -406,11 +406,22 @@ extern "C" int ustrun_unet_backward(const ustrun_unet_desc_t* d, const float* x,
 // while the encoder half still runs, and that of down4's while the high-resolution encoder layers run.
 extern "C" int ustrun_unet_backward_part(const ustrun_unet_desc_t* d, const float* x, const float* dlogits, void* workspace,
                                          void* scratch, float* const* grads, int accumulate, int which, ustrun_stream_t s) {
+    USTRUN_CHECK(dlogits, "unet_backward: null pointer");
+    return ustrun_unet_backward_io(d, x, dlogits, nullptr, workspace, scratch, grads, accumulate, which, nullptr, s);
+}
+
+// ... and with the gradient of the feature output coming in (dfeat: added to the head's da in front of layer 17's BatchNorm
+// backward) and the gradient of the network input going out (dx: the first convolution's input gradient, behind layer 0)
+extern "C" int ustrun_unet_backward_io(const ustrun_unet_desc_t* d, const float* x, const float* dlogits, const float* dfeat,
+                                       void* workspace, void* scratch, float* const* grads, int accumulate, int which, float* dx,
+                                       ustrun_stream_t s) {
     USTRUN_CHECK(which >= 0 && which <= 4, "unet_backward: part %d", which);
     Plan p; USTRUN_TRY(make_plan(d, p));
     ShortLastPass declared_tail(p.T > 0);
-    USTRUN_CHECK(x && dlogits && workspace && scratch && grads && d->packed, "unet_backward: null pointer");
+    USTRUN_CHECK(x && (dlogits || dfeat || which > 1) && workspace && scratch && grads && d->packed, "unet_backward: null pointer");
     USTRUN_CHECK(d->train, "unet_backward: forward must have run in train mode");
+    USTRUN_CHECK(!dx || (p.C <= 4 && p.base % 8 == 0 && p.base <= 64),
+                 "unet_backward: the input gradient is built for C <= 4 and base a multiple of 8 up to 64 (C=%d base=%d)", p.C, p.base);
     const char* ws = (const char*)workspace;
     char* sc = (char*)scratch;
     const float* pk = (const float*)d->packed;
@@ -419,16 +430,26 @@ extern "C" int ustrun_unet_backward_part(const ustrun_unet_desc_t* d, const floa
     // (everything the backward reads starts behind the leading passes: image p.ob of every tensor, pass p.L of every constant table)
     auto affp = [&](int k) { return (const float*)(ws + p.aff_off[k]) + 4L * p.cout[k] * p.L; };
     auto yb = [&](int k) { return ws + p.y_off[k] + (long)p.ob * p.Hs[p.lvl[k]] * p.Ws[p.lvl[k]] * p.cout[k] * p.esz; };
-    dlogits += (long)p.ob * p.K * p.H * p.W;
+    if (dlogits) dlogits += (long)p.ob * p.K * p.H * p.W;
+    if (dfeat) dfeat += (long)p.ob * p.base * p.H * p.W;
     const int dt = d->dtype;
 
     int head_bn_rows = 0;       // > 0: the head kernel also formed layer 17's BatchNorm-backward sums (rows per pass, in `part`)
     if (which <= 1) {   // head: all passes in one launch (blockIdx.y = pass: its BatchNorm constants on load)
         const int C = p.cout[17];
         const long gpix = (long)p.gN * p.H * p.W;
+        // (with dfeat the head's fused sums would miss it: the head runs without them -- the route bit 23 takes -- and layer 17's
+        // BatchNorm backward runs its reduce pass over the summed da)
+        if (dlogits)
         USTRUN_TRY(head_bwd_passes(dlogits, yb(17), affp(17), affp(17) + C, gpix, p.H * p.W, C, p.K, d->head_w,
                                    sc + p.da_off[17], grads[p.gi_head], grads[p.gi_head + 1], accumulate, part, p.part_bytes, dt, p.Gb, 4L * C,
-                                   (hipStream_t)s, (g_debug_flags & 8388608) ? nullptr : &head_bn_rows));
+                                   (hipStream_t)s, ((g_debug_flags & 8388608) || dfeat) ? nullptr : &head_bn_rows));
+        else if (!accumulate) {     // no gradient at the logits: the head's parameters get zeros
+            hipError_t e = hipMemsetAsync(grads[p.gi_head], 0, sizeof(float) * p.K * C, (hipStream_t)s);
+            if (e == hipSuccess) e = hipMemsetAsync(grads[p.gi_head + 1], 0, sizeof(float) * p.K, (hipStream_t)s);
+            USTRUN_CHECK(e == hipSuccess, "unet_backward: zeroing the head's gradients: %s", hipGetErrorString(e));
+        }
+        if (dfeat) USTRUN_TRY(feat_grad_add(dfeat, sc + p.da_off[17], p.Nb, p.H * p.W, C, dlogits != nullptr, dt, (hipStream_t)s));
     }
     // layers 17..10 = decoder, 9..8 = down4 (57 of the encoder's 75 MB of gradients, and the first to finish), 7..0 = the rest
     const int i_hi = which <= 1 ? 17 : (which == 4 ? 7 : 9);
@@ -468,7 +489,19 @@ extern "C" int ustrun_unet_backward_part(const ustrun_unet_desc_t* d, const floa
         prof_set_tag(200 + i, p.Nb);
         USTRUN_TRY(ustrun_conv3x3_wgrad(srcs, ns, da, p.Nb, H, W, C, grads[gi], accumulate, part, p.part_bytes, dt, s));
         prof_set_tag(-1, 0);
-        if (i == 0) break;
+        if (i == 0) {
+            if (dx) {       // the network input's gradient: zero for the leading passes and the tail pass, which get none
+                const long img = (long)p.C * p.H * p.W;
+                hipError_t e = p.ob ? hipMemsetAsync(dx, 0, sizeof(float) * img * p.ob, (hipStream_t)s) : hipSuccess;
+                if (e == hipSuccess && p.T) e = hipMemsetAsync(dx + img * (p.ob + p.Nb), 0, sizeof(float) * img * p.T, (hipStream_t)s);
+                USTRUN_CHECK(e == hipSuccess, "unet_backward: zeroing dx: %s", hipGetErrorString(e));
+                prof_set_tag(100, p.Nb);
+                const int rc = ustrun_conv_first_dgrad(da, d->conv_w[0], p.Nb, H, W, C, p.C, dx + img * p.ob, dt, s);
+                prof_set_tag(-1, 0);
+                USTRUN_TRY(rc);
+            }
+            break;
+        }
         const float* wd = pk + p.wd_off[i];
         struct Untag { ~Untag() { prof_set_tag(-1, 0); } } untag_;
         prof_set_tag(100 + i, p.Nb);

@@ -143,6 +143,8 @@ SIGNATURES = {
     "ustrun_unet_forward": (i32, [PDesc, fp, fp, fp, vp, vp]),
     "ustrun_unet_backward": (i32, [PDesc, fp, fp, vp, vp, C.POINTER(vp), i32, vp]),
     "ustrun_unet_backward_part": (i32, [PDesc, fp, fp, vp, vp, C.POINTER(vp), i32, i32, vp]),
+    "ustrun_unet_backward_io": (i32, [PDesc, fp, fp, fp, vp, vp, C.POINTER(vp), i32, i32, fp, vp]),
+    "ustrun_conv_first_dgrad": (i32, [vp, fp, i32, i32, i32, i32, i32, fp, i32, vp]),
 }
 
 _lib = None

@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 
@@ -118,42 +119,55 @@ def _current_debug_flags(lib):
 
 
 class _UNetFn(torch.autograd.Function):
+    """x and the parameters are the differentiable inputs; logits and (feature=True) feat the differentiable outputs, as in the
+    reference, where both are ordinary autograd tensors (networks/unet_model.py:25-39)."""
+
     @staticmethod
     def forward(ctx, x, model, feature, groups, tail, lead, *params):
+        x = x.contiguous()
         logits, feat, ws, d = _run_forward(model, x, feature, groups, tail, lead)
         ctx.model, ctx.ws, ctx.desc, ctx.x = model, ws, d, x
         # ustrun_debug_flags is per calling thread and autograd runs backward() on a thread of its own: the backward runs under
         # the flags the forward ran under (some of them shape the plan both halves share)
         ctx.debug_flags = _current_debug_flags(L.lib())
         ctx.nparams = len(params)
+        ctx.set_materialize_grads(False)        # an output without a loss arrives as None and costs nothing
         if feature:
-            ctx.mark_non_differentiable(feat)
             return logits, feat
         return logits
 
     @staticmethod
-    def backward(ctx, dlogits, *unused):
+    @once_differentiable
+    def backward(ctx, dlogits, dfeat=None):
         model, d = ctx.model, ctx.desc
+        if dlogits is None and dfeat is None:
+            return (None,) * (6 + ctx.nparams)
         lib = L.lib()
         restore = lib.ustrun_debug_flags(ctx.debug_flags[0]), lib.ustrun_debug_flags2(ctx.debug_flags[1])
         try:
-            return _UNetFn._backward(ctx, lib, model, d, dlogits)
+            return _UNetFn._backward(ctx, lib, model, d, dlogits, dfeat)
         finally:
             lib.ustrun_debug_flags(restore[0])
             lib.ustrun_debug_flags2(restore[1])
 
     @staticmethod
-    def _backward(ctx, lib, model, d, dlogits):
-        dlogits = dlogits.contiguous()
+    def _backward(ctx, lib, model, d, dlogits, dfeat):
+        dlogits = None if dlogits is None else dlogits.contiguous()
+        dfeat = None if dfeat is None else dfeat.contiguous()
+        dev = ctx.x.device
+        for t, what in ((dlogits, "logits"), (dfeat, "features")):
+            if t is not None and t.dtype != torch.float32:
+                raise RuntimeError(f"UNet: the gradient of the {what} must be float32")
         nbytes = lib.ustrun_unet_bwd_scratch_bytes(C.byref(d))
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dlogits.device)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        dx = torch.empty_like(ctx.x) if ctx.needs_input_grad[0] else None
         params = model_params(model)
         sink = getattr(model, "_ustrun_grad_sink", None)
         if sink is not None:
             targets, accumulate = sink, 0 if getattr(model, "_ustrun_sink_fresh", True) else 1
             model._ustrun_sink_fresh = False
         else:
-            flat = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=dlogits.device)
+            flat = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
             targets, o = [], 0
             for p in params:
                 targets.append(flat[o:o + p.numel()].view_as(p))
@@ -161,22 +175,25 @@ class _UNetFn(torch.autograd.Function):
             accumulate = 0
         arr = (C.c_void_p * len(targets))(*[t.data_ptr() for t in targets])
         split = getattr(model, "_ustrun_backward_split_hook", None)
+
+        def run(part):      # (null dfeat and dx: launch for launch ustrun_unet_backward / _part, which forward here with nulls)
+            L.check(lib.ustrun_unet_backward_io(C.byref(d), ctx.x.data_ptr(), L.ptr(dlogits), L.ptr(dfeat), ctx.ws.data_ptr(),
+                                                scratch.data_ptr(), arr, accumulate, part, L.ptr(dx), stream_ptr()),
+                    "ustrun_unet_backward_io")
+
         if split is None:
-            L.check(lib.ustrun_unet_backward(C.byref(d), ctx.x.data_ptr(), dlogits.data_ptr(), ctx.ws.data_ptr(),
-                                             scratch.data_ptr(), arr, accumulate, stream_ptr()), "ustrun_unet_backward")
+            run(0)
         else:       # head + decoder, hand the (now final) decoder gradients to the caller, then the encoder -- down4
             mid = getattr(model, "_ustrun_backward_mid_hook", None)        # first when the caller wants its gradients early
             for part in ((1, 3, 4) if mid is not None else (1, 2)):
-                L.check(lib.ustrun_unet_backward_part(C.byref(d), ctx.x.data_ptr(), dlogits.data_ptr(), ctx.ws.data_ptr(),
-                                                      scratch.data_ptr(), arr, accumulate, part, stream_ptr()),
-                        "ustrun_unet_backward_part")
+                run(part)
                 if part == 1:
                     split()
                 elif part == 3:
                     mid()
         ctx.ws = None
         grads = (None,) * ctx.nparams if sink is not None else tuple(targets)
-        return (None, None, None, None, None, None) + grads
+        return (dx, None, None, None, None, None) + grads
 
 
 def _run_forward(model, x, feature, groups=1, tail=0, lead=0):
@@ -215,9 +232,12 @@ def unet_forward(model, x, feature=False, groups=1, tail=0, lead=0):
     the returned logits cover the passes in front of it.  lead > 0: the first `lead` passes get no gradient (their rows of the
     logits' gradient are ignored): a no-grad forward that must come first in BatchNorm order rides in the same call."""
     params = model_params(model)
-    needs_grad = torch.is_grad_enabled() and model.training and any(p.requires_grad for p in params)
-    if x.requires_grad:
-        raise NotImplementedError("gradient w.r.t. the network input is not on the hot path (train.py never needs it)")
+    wants_dx = torch.is_grad_enabled() and x.requires_grad
+    if wants_dx and not model.training:
+        raise NotImplementedError("UNet: the eval-mode backward (running statistics) is not built: gradient w.r.t. the network "
+                                  "input needs model.train()")
+    # (the node is recorded for the input alone too: every parameter frozen, x.requires_grad -- adversarial perturbation, saliency)
+    needs_grad = torch.is_grad_enabled() and model.training and (wants_dx or any(p.requires_grad for p in params))
     if needs_grad:
         return _UNetFn.apply(x, model, feature, groups, tail, lead, *params)
     logits, feat, _, _ = _run_forward(model, x, feature, groups, tail, lead)
