@@ -602,6 +602,66 @@ typedef struct ustrun_prof_rec {
 } ustrun_prof_rec_t;
 int64_t ustrun_profile_records(ustrun_prof_rec_t* host_out, int64_t max_records);
 
+/* ------------------------------------------------------------------------------------------
+ * Data augmentation of resident image pools (csrc/augment.hip).  The reference runs
+ * these per sample in PIL / scipy on loader workers (dataloaders/dataloader.py:95-107,
+ * dataloaders/custom_transforms.py); here a batch is a set of uint8 HWC buffers on the device
+ * and every stage reads uint8 and writes uint8 where the reference quantises.
+ *   images [B][H][W][C] (C = 1 or 3), labels [B][H][W][Cl] (Cl = 1 or 3), H, W <= 1024.
+ *   `params` is the batch's int32 parameter block: sample b reads params + b * stride; a float
+ *   or double parameter is stored as its bit pattern (doubles: low word first).  Word 0 of every
+ *   stage's row is its gate: 0 = the sample is copied.  The host draws the rows
+ *   (ustrun/datasets.py: AugmentSampler), the only host-to-device copy of a step.
+ * ---------------------------------------------------------------------------------------- */
+/* batch buffers out of the pools: img_out[b] = images[idx[b]], lab_out[b] = labels[idx[b]] (the DataLoader's
+ * index sampling + default collate, train.py:490-491).  An index outside [0, n_pool) copies nothing.           */
+int ustrun_aug_gather(const uint8_t* images, const uint8_t* labels, const int32_t* idx, int64_t n_pool, int32_t B,
+                      int64_t img_bytes, int64_t lab_bytes, uint8_t* img_out, uint8_t* lab_out, ustrun_stream_t stream);
+/* RandomScaleCrop (custom_transforms.py:529-550) + RandomCrop (:311-344): PIL resize((w, h), BILINEAR) of the image
+ * (fixed-point two-tap triangle, horizontal then vertical pass, uint8 after each), resize(NEAREST) of the label, the
+ * border of RandomCrop's padded branch (image 0, label `fill`), then the P x P window at (x1, y1).  Only the window
+ * is sampled.  Row: {gate, w, h, pad, x1, y1, fill, 0}; gate 0 -> w = Ws, h = Hs (pad and the window still apply).
+ * fill packs one byte per label channel, channel c = (fill >> 8c) & 255: PIL's reading of an integer colour.      */
+int ustrun_aug_scale_crop(const uint8_t* img, const uint8_t* lab, const int32_t* params, int32_t stride, int32_t B,
+                          int32_t Hs, int32_t Ws, int32_t C, int32_t Cl, int32_t P, uint8_t* img_out, uint8_t* lab_out,
+                          ustrun_stream_t stream);
+/* RandomScaleRotate (custom_transforms.py:507-526) with RandomHorizontalFlip (:387-397) folded into the output
+ * address: PIL rotate(deg, BILINEAR) about the centre for the image (double arithmetic, truncation, 0 outside),
+ * rotate(deg, NEAREST, fillcolor) for the label (PIL's 16.16 fixed-point walk).  Row: {gate, flip, fill, 0,
+ * fixed a0..a5 (6 words), the affine matrix a..f as doubles (12 words)}: the host forms the matrix as PIL does.     */
+int ustrun_aug_rotate(const uint8_t* img, const uint8_t* lab, const int32_t* params, int32_t stride, int32_t B,
+                      int32_t H, int32_t W, int32_t C, int32_t Cl, uint8_t* img_out, uint8_t* lab_out,
+                      ustrun_stream_t stream);
+/* The displacement fields of elastic_transform (custom_transforms.py:207-225): two uniform(-1, 1) fields per gated
+ * sample, each smoothed by a separable Gaussian (sigma = 0.08 H, radius int(4 sigma + 0.5), zeros outside; axis 0
+ * first) and scaled by 2 H.  noise == NULL: the fields come from a counter-based hash of (seed, sample, field,
+ * pixel) -- the reference draws them from an unseeded RandomState; noise != NULL (tests): [B][2][H][W] floats.
+ * field, work: [B][2][H][W] floats each.  Row: {gate}.  H != W is an error (the reference's index convention is
+ * only consistent for square patches).                                                                           */
+int ustrun_aug_elastic_field(const float* noise, int64_t seed, const int32_t* params, int32_t stride, int32_t B,
+                             int32_t H, int32_t W, float* field, float* work, ustrun_stream_t stream);
+/* the generator's [B][2][H][W] values on their own (tests): what ustrun_aug_elastic_field smooths when noise == NULL */
+int ustrun_aug_elastic_noise(int64_t seed, int32_t B, int32_t H, int32_t W, float* noise, ustrun_stream_t stream);
+/* elastic_transform's resampling (custom_transforms.py:227-255): out[i][j] = in(i + field[b][0][i][j],
+ * j + field[b][1][i][j]); image: scipy map_coordinates(order=1) of a uint8 array, constant 0 outside, rounded to
+ * nearest (the result takes the input's dtype); label: order=0, mode='nearest'.  Row: {gate}.  H != W is an error. */
+int ustrun_aug_elastic_warp(const uint8_t* img, const uint8_t* lab, const float* field, const int32_t* params,
+                            int32_t stride, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Cl, uint8_t* img_out,
+                            uint8_t* lab_out, ustrun_stream_t stream);
+/* bytes of `work` ustrun_aug_strong needs */
+int64_t ustrun_aug_strong_work_bytes(int32_t B, int32_t H, int32_t W, int32_t C);
+/* The strong view (train.py:453-457): ImageEnhance.Brightness (blend with black), ImageEnhance.Contrast (blend with
+ * the grey int(mean(L) + 0.5) of the brightened image; one block per image, integer sum), GaussianBlur
+ * (custom_transforms.py:78-118: / 255, reflection pad r, 2r + 1 taps down then across, * 255, truncated).
+ * Row: {gate, brightness, contrast, sigma} (floats as bits); gate bit 0 = brightness and contrast, bit 1 = blur (the
+ * reference applies all three: 3).  r < min(H, W), r <= 63.                                                        */
+int ustrun_aug_strong(const uint8_t* img, const int32_t* params, int32_t stride, int32_t B, int32_t H, int32_t W,
+                      int32_t C, int32_t r, uint8_t* img_out, void* work, int64_t work_bytes, ustrun_stream_t stream);
+/* Normalize_tf + ToTensor (custom_transforms.py:650-684, :728-753): xw, xs [B][C][H][W] f32 = x / 127.5 - 1 of the
+ * weak and the strong image (strong, xs may be NULL), y [B][H][W][Cl] f32 = the label's byte values.              */
+int ustrun_aug_finish(const uint8_t* weak, const uint8_t* strong, const uint8_t* lab, int32_t B, int32_t H, int32_t W,
+                      int32_t C, int32_t Cl, float* xw, float* xs, float* y, ustrun_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,11 +2,11 @@
 """test.py -- MI355X build of the reference's evaluation driver (test.py:19-250).
 
 Same command line (flag names and defaults of test.py:19-32; `--dataset` also accepts BUSI, which the reference
-trains but does not list here); additive flags: --synthetic, --test_batches, --backend_dtype, --seed, --surface_metrics.  Loads
+trains but does not list here); additive flags: --synthetic, --data_root, --test_batches, --backend_dtype, --seed, --surface_metrics.  Loads
 `../model/<dataset>/<save_name>/unet_avg_dice_best_model.pth` (a plain state_dict with the reference's keys, test.py:241)
 and prints the per-domain and mean Dice of ustrun.evaluate.validate; `--surface_metrics 1` adds the reference's
-dc / jc / hd / asd lines (test.py:117-136,160-176), computed on the device instead of with medpy.  The dataset classes are
-outside this build: batches come from the seeded synthetic generator unless a loader is plugged into `make_loaders`.
+dc / jc / hd / asd lines (test.py:117-136,160-176), computed on the device instead of with medpy.  Batches come from the
+seeded synthetic generator, or with --synthetic 0 from the test splits under --data_root (ustrun/datasets.py).
 """
 import argparse
 import logging
@@ -31,6 +31,7 @@ parser.add_argument('--save_img', action='store_true')
 # additive flags of this build
 parser.add_argument('--synthetic', type=int, default=1)
 parser.add_argument('--test_batches', type=int, default=8, help='synthetic batches per domain')
+parser.add_argument('--data_root', type=str, default='../../data', help='--synthetic 0: where the dataset folders are')
 parser.add_argument('--backend_dtype', default='f32', choices=['f32', 'f32x3', 'bf16', 'f16'])
 parser.add_argument('--seed', type=int, default=1337)
 parser.add_argument('--load_path', type=str, default='', help='state_dict file (default: the reference\'s path)')
@@ -42,9 +43,9 @@ DOMAINS = {"fundus": 4, "prostate": 6, "MNMS": 4, "BUSI": 1}     # test.py:209-2
 
 
 def make_loaders(args, C, H):
-    if not args.synthetic:
-        raise SystemExit("the dataset classes of the reference (dataloaders/) are outside this build's scope; "
-                         "run with --synthetic 1 or plug a loader in here")
+    if not args.synthetic:      # the reference's per-domain test splits (test.py:222-230), resident, no augmentation
+        from ustrun import datasets
+        return datasets.test_loaders(datasets.test_datasets(args, H, "cuda"), args.test_bs)
     from ustrun import synthetic
     return synthetic.test_loaders(args.dataset, args.domain_num, args.test_batches, args.test_bs, C, H, args.seed)
 

@@ -3,12 +3,14 @@
 
 Keeps the reference's command line (train.py:38-79: same flag names and defaults); new flags are
 additive (--synthetic, --backend_dtype, --data_root, --fft, --log_every).  The step itself is
-ustrun.trainer.SSLTrainer (HIP kernels through libustrun.so).  Data loading, augmentation,
-the medpy metrics and tensorboard logging are outside this build's scope; the Dice
-validation at every epoch end is ustrun.evaluate.validate: batches
-come from the seeded synthetic generator unless a loader is plugged in through `make_loaders`.
+ustrun.trainer.SSLTrainer (HIP kernels through libustrun.so).  Tensorboard logging is outside
+this build's scope; the Dice validation at every epoch end is
+ustrun.evaluate.validate.  Batches come from the seeded synthetic generator (--synthetic 1, the
+default) or from the reference's image folders under --data_root (--synthetic 0: decoded once
+into resident pools, augmented on the device, ustrun/datasets.py).
 
 Single GPU:   python train.py --dataset fundus --save_name run0 --synthetic 1
+Image folders: python train.py --dataset fundus --synthetic 0 --data_root ../../data --lb_domain 1 --lb_num 20
 Data parallel: python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py ...
 """
 import argparse
@@ -60,7 +62,7 @@ parser.add_argument('--LB', default=0.01, type=float)
 parser.add_argument('--increase', default=1.0005, type=float)
 parser.add_argument('--queue_len', default=10, type=int)
 # additive flags of this build
-parser.add_argument('--synthetic', type=int, default=1, help='seeded synthetic batches (SURVEY.md 8d)')
+parser.add_argument('--synthetic', type=int, default=1, help='1: seeded synthetic batches (SURVEY.md 8d); 0: the image folders under --data_root')
 parser.add_argument('--amp_dtype', default='fp16', choices=['fp16', 'bf16'],
                     help="storage / matrix-core type under --amp 1: 'fp16' = the reference's torch.cuda.amp autocast + GradScaler "
                          "(train.py:30,551-552,842-845: IEEE half, dynamic loss scale on the device), 'bf16' = bfloat16, no loss scale")
@@ -92,13 +94,18 @@ def compute_dtype(args):
 
 
 def make_loaders(args, C, H, dev=None):
-    """-> iterator of (lb_x_w, lb_y, ulb_x_w, ulb_x_s, ulb_y) CPU tensors."""
-    if not args.synthetic:
-        raise SystemExit("the PIL/scipy dataset pipeline of the reference (dataloaders/) is outside this build's scope; "
-                         "run with --synthetic 1 or plug a loader in here")
-    from ustrun import synthetic
+    """-> iterator of (lb_x_w, lb_y, ulb_x_w, ulb_x_s, ulb_y) tensors: CPU ones from the synthetic generator (device ones when its
+    pool is resident), device ones from the image folders under --data_root (--synthetic 0: ustrun.datasets)."""
     from ustrun.ddp import env_world
     rank = env_world()[0]
+    if not args.synthetic:
+        # the reference's datasets and labelled / unlabelled split (train.py:464-491), decoded once into resident pools;
+        # weak augmentation for the labelled batch, weak then strong for the unlabelled one (dataloader.py:103-107), on the device
+        from ustrun import datasets
+        lb_ds, ulb_ds = datasets.train_datasets(args, H, dev if dev is not None else "cuda")
+        yield from datasets.ResidentLoader(lb_ds, ulb_ds, args.label_bs, args.unlabel_bs, args.seed, rank)
+        return
+    from ustrun import synthetic
     step = 0
     if args.synthetic_pool > 0:       # a pool of distinct seeded batches, generated once and cycled: the host generator
         pool = [synthetic.batch(args.dataset, args.label_bs, C, H, args.seed + 100003 * rank + i)   # (0.2 s per batch)
@@ -111,6 +118,15 @@ def make_loaders(args, C, H, dev=None):
     while True:
         yield synthetic.batch(args.dataset, args.label_bs, C, H, args.seed + 100003 * rank + step)
         step += 1
+
+
+def make_test_loaders(args, C, H, dev=None):
+    """One iterable of (image, raw label) batches per domain for ustrun.evaluate.validate (train.py:486-494)."""
+    if not args.synthetic:
+        from ustrun import datasets
+        return datasets.test_loaders(datasets.test_datasets(args, H, dev if dev is not None else "cuda"), args.test_bs)
+    from ustrun import synthetic
+    return synthetic.test_loaders(args.dataset, min(args.domain_num, 2), 4, args.test_bs, C, H, args.seed + 17)
 
 
 def train(args, snapshot_path):
@@ -154,9 +170,8 @@ def train(args, snapshot_path):
                          increase=args.increase, queue_len=args.queue_len, num_eval_iter=args.num_eval_iter,
                          grad_allreduce=ddp.make_grad_allreduce(world), world_size=world, fft=args.fft, patch_size=H)
     loader = make_loaders(args, C, H, dev)
-    from ustrun import synthetic
     from ustrun.evaluate import validate
-    test_loaders = synthetic.test_loaders(args.dataset, min(args.domain_num, 2), 4, args.test_bs, C, H, args.seed + 17)
+    test_loaders = make_test_loaders(args, C, H, dev)
     best = {"avg": 0.0, "iter": 0, "stu_avg": 0.0, "stu_iter": 0}
     start_epoch = 0
     if args.load:      # train.py:542-548: resume from the run's own checkpoint.pth (--load_path is parsed but unused there too)

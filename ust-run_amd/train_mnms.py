@@ -7,6 +7,7 @@ is train.py's: the reference's two drivers differ only in the label decoding (tr
 -> classes 1..3), the 4-class softmax head and the 288 x 288 patch, all of which ustrun.trainer.DATASETS["MNMS"] carries.
 
     python train_mnms.py --save_name run0 --synthetic 1
+    python train_mnms.py --save_name run0 --synthetic 0 --data_root ../../data      (the vendorA..D folders under <data_root>/mnms)
 """
 import logging
 import os

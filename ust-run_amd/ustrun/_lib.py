@@ -145,6 +145,15 @@ SIGNATURES = {
     "ustrun_unet_backward_part": (i32, [PDesc, fp, fp, vp, vp, C.POINTER(vp), i32, i32, vp]),
     "ustrun_unet_backward_io": (i32, [PDesc, fp, fp, fp, vp, vp, C.POINTER(vp), i32, i32, fp, vp]),
     "ustrun_conv_first_dgrad": (i32, [vp, fp, i32, i32, i32, i32, i32, fp, i32, vp]),
+    "ustrun_aug_gather": (i32, [vp, vp, vp, i64, i32, i64, i64, vp, vp, vp]),
+    "ustrun_aug_scale_crop": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "ustrun_aug_rotate": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "ustrun_aug_elastic_field": (i32, [fp, i64, vp, i32, i32, i32, i32, fp, fp, vp]),
+    "ustrun_aug_elastic_noise": (i32, [i64, i32, i32, i32, fp, vp]),
+    "ustrun_aug_elastic_warp": (i32, [vp, vp, fp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "ustrun_aug_strong_work_bytes": (i64, [i32, i32, i32, i32]),
+    "ustrun_aug_strong": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i64, vp]),
+    "ustrun_aug_finish": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, fp, fp, fp, vp]),
 }
 
 _lib = None
