@@ -290,16 +290,15 @@ __global__ void bn_relu_apply_kernel(const float* __restrict__ y, int esz, const
 __global__ __launch_bounds__(256) void act16_kernel(const elt_t* __restrict__ y, const float* __restrict__ scale,
                                                     const float* __restrict__ shift, int relu, int gN, long gstride,
                                                     long npix, int HW, int C, elt_t* __restrict__ out) {
-    typedef __attribute__((ext_vector_type(8))) elt_t bf16x8v;
     const int CV = C / 8, PPB = 256 / CV;
     const int cv = threadIdx.x % CV, pl = threadIdx.x / CV;
     if (pl >= PPB) return;
     constexpr int U = 4;
     const long stride = (long)gridDim.x * PPB;
     for (long p0 = (long)blockIdx.x * PPB + pl; p0 < npix; p0 += U * stride) {
-        bf16x8v r[U];
+        bf16x8 r[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) { const long p = p0 + u * stride; r[u] = *(const bf16x8v*)(y + (p < npix ? p : npix - 1) * C + cv * 8); }
+        for (int u = 0; u < U; ++u) { const long p = p0 + u * stride; r[u] = *(const bf16x8*)(y + (p < npix ? p : npix - 1) * C + cv * 8); }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const long p = p0 + u * stride;
@@ -308,14 +307,14 @@ __global__ __launch_bounds__(256) void act16_kernel(const elt_t* __restrict__ y,
             const float* ps = scale + grp * gstride + cv * 8;
             const float* pb = shift + grp * gstride + cv * 8;
             const f32x4 s0 = *(const f32x4*)ps, s1 = *(const f32x4*)(ps + 4), b0 = *(const f32x4*)pb, b1 = *(const f32x4*)(pb + 4);
-            bf16x8v o;
+            bf16x8 o;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 float a = (float)r[u][j] * (j < 4 ? s0[j & 3] : s1[j & 3]) + (j < 4 ? b0[j & 3] : b1[j & 3]);
                 a = relu ? fmaxf(a, 0.f) : a;
                 o[j] = (elt_t)a;
             }
-            *(bf16x8v*)(out + p * C + cv * 8) = o;
+            *(bf16x8*)(out + p * C + cv * 8) = o;
         }
     }
 }
@@ -330,7 +329,6 @@ __global__ __launch_bounds__(256) void pool_act_kernel(const float* __restrict__
                                                       int N, int H, int W, int C, float* __restrict__ out,
                                                       elt_t* __restrict__ act) {
     constexpr int V = ESZ == 2 ? 8 : 4;             // channels per thread: one 16-byte load per window pixel
-    typedef __attribute__((ext_vector_type(8))) elt_t bf16x8v;
     const int Hp = H / 2, Wp = W / 2, CV = C / V;
     // a thread keeps its channel group (256 % CV == 0 for the power-of-two channel counts; else it re-derives it)
     const long npix = (long)N * Hp * Wp;
@@ -355,9 +353,9 @@ __global__ __launch_bounds__(256) void pool_act_kernel(const float* __restrict__
         const long base = (((long)n * H + 2 * py) * W + 2 * px) * C + cv * V;
         float v[4][V];
         if (ESZ == 2) {
-            bf16x8v r[4];
+            bf16x8 r[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) r[q] = *(const bf16x8v*)((const elt_t*)y + base + ((q >> 1) * (long)W + (q & 1)) * C);
+            for (int q = 0; q < 4; ++q) r[q] = *(const bf16x8*)((const elt_t*)y + base + ((q >> 1) * (long)W + (q & 1)) * C);
 #pragma unroll
             for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -384,18 +382,18 @@ __global__ __launch_bounds__(256) void pool_act_kernel(const float* __restrict__
         if (ESZ == 2 && act) {                      // the window's four activated pixels, as the concat convolution will read them
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                bf16x8v a8;
+                bf16x8 a8;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) a8[j] = (elt_t)v[q][j % V];
-                *(bf16x8v*)(act + base + ((q >> 1) * (long)W + (q & 1)) * C) = a8;
+                *(bf16x8*)(act + base + ((q >> 1) * (long)W + (q & 1)) * C) = a8;
             }
         }
         const long ob = (((long)n * Hp + py) * Wp + px) * C + cv * V;
         if (ESZ == 2) {                                     // one 16-byte store
-            bf16x8v o8;
+            bf16x8 o8;
 #pragma unroll
             for (int j = 0; j < 8; ++j) o8[j] = (elt_t)m[j % V];
-            *(bf16x8v*)((elt_t*)out + ob) = o8;
+            *(bf16x8*)((elt_t*)out + ob) = o8;
         } else {
 #pragma unroll
             for (int h = 0; h < V / 4; ++h) st4t<ESZ>(out, ob + 4 * h, (f32x4){m[4 * h], m[4 * h + 1], m[4 * h + 2], m[4 * h + 3]});
@@ -723,9 +721,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* da, cons
 // their occupancy that is about half of what 8 TB/s x the memory latency asks of a CU, and the plain apply pass ran at
 // 4.8-5.1 TB/s where the pooled one (nine loads per thread) reaches 5.5.  Here a lane owns 8 channels of a pixel: thread =
 // (octet tid % G8, pixel lane tid / G8), G8 = C / 8 a power of two <= 256; the arithmetic is the same per element.
-typedef __attribute__((ext_vector_type(8))) elt_t bf16x8_bn;
 struct F8 { f32x4 lo, hi; };
-__device__ __forceinline__ F8 up8(bf16x8_bn v) {
+__device__ __forceinline__ F8 up8(bf16x8 v) {
     return F8{(f32x4){(float)v[0], (float)v[1], (float)v[2], (float)v[3]}, (f32x4){(float)v[4], (float)v[5], (float)v[6], (float)v[7]}};
 }
 __device__ __forceinline__ F8 ld8f(const float* p) { return F8{*(const f32x4*)p, *(const f32x4*)(p + 4)}; }
@@ -745,9 +742,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_x8_kernel(const elt_t* __res
     const long stride = (long)gridDim.x * PL;
     constexpr int U = 2;
     long w = (long)blockIdx.x * PL + pl;
-    auto one = [&](bf16x8_bn yb, bf16x8_bn db) {
+    auto one = [&](bf16x8 yb, bf16x8 db) {
         const F8 yv = up8(yb), dv = up8(db);
-        bf16x8_bn o;
+        bf16x8 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float al = yv.lo[j] * sc.lo[j] + sh.lo[j], ah = yv.hi[j] * sc.hi[j] + sh.hi[j];
@@ -758,14 +755,14 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_x8_kernel(const elt_t* __res
         return o;
     };
     for (; w + (U - 1) * stride < npix; w += U * stride) {
-        bf16x8_bn yb[U], db[U];
+        bf16x8 yb[U], db[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) { yb[u] = *(const bf16x8_bn*)(y + (w + u * stride) * C + c); db[u] = *(const bf16x8_bn*)(da + (w + u * stride) * C + c); }
+        for (int u = 0; u < U; ++u) { yb[u] = *(const bf16x8*)(y + (w + u * stride) * C + c); db[u] = *(const bf16x8*)(da + (w + u * stride) * C + c); }
 #pragma unroll
-        for (int u = 0; u < U; ++u) *(bf16x8_bn*)(dy + (w + u * stride) * C + c) = one(yb[u], db[u]);
+        for (int u = 0; u < U; ++u) *(bf16x8*)(dy + (w + u * stride) * C + c) = one(yb[u], db[u]);
     }
     for (; w < npix; w += stride)
-        *(bf16x8_bn*)(dy + w * C + c) = one(*(const bf16x8_bn*)(y + w * C + c), *(const bf16x8_bn*)(da + w * C + c));
+        *(bf16x8*)(dy + w * C + c) = one(*(const bf16x8*)(y + w * C + c), *(const bf16x8*)(da + w * C + c));
 }
 
 __global__ __launch_bounds__(256) void bn_bwd_reduce_x8_kernel(const elt_t* __restrict__ da, const elt_t* __restrict__ y,
@@ -785,7 +782,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_x8_kernel(const elt_t* __re
     const long stride = (long)gridDim.x * PL;
     constexpr int U = 4;
     long w = (long)blockIdx.x * PL + pl;
-    auto acc1 = [&](bf16x8_bn yb, bf16x8_bn db) {
+    auto acc1 = [&](bf16x8 yb, bf16x8 db) {
         const F8 yv = up8(yb), dv = up8(db);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -796,13 +793,13 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_x8_kernel(const elt_t* __re
         }
     };
     for (; w + (U - 1) * stride < npix; w += U * stride) {       // four pixels' loads in flight, sums in ascending pixel order
-        bf16x8_bn yb[U], db[U];
+        bf16x8 yb[U], db[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) { yb[u] = *(const bf16x8_bn*)(y + (w + u * stride) * C + c); db[u] = *(const bf16x8_bn*)(da + (w + u * stride) * C + c); }
+        for (int u = 0; u < U; ++u) { yb[u] = *(const bf16x8*)(y + (w + u * stride) * C + c); db[u] = *(const bf16x8*)(da + (w + u * stride) * C + c); }
 #pragma unroll
         for (int u = 0; u < U; ++u) acc1(yb[u], db[u]);
     }
-    for (; w < npix; w += stride) acc1(*(const bf16x8_bn*)(y + w * C + c), *(const bf16x8_bn*)(da + w * C + c));
+    for (; w < npix; w += stride) acc1(*(const bf16x8*)(y + w * C + c), *(const bf16x8*)(da + w * C + c));
     red[0][threadIdx.x] = s1.lo; red[1][threadIdx.x] = s1.hi; red[2][threadIdx.x] = s2.lo; red[3][threadIdx.x] = s2.hi;
     __syncthreads();
     if (pl == 0) {                                              // fixed order over the block's pixel lanes

@@ -18,9 +18,6 @@
 namespace ustrun {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) elt_t bf16x8;
-typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
 
 __device__ __forceinline__ int fastmod(int v, int d, float inv) {      // v mod d for 0 <= v < 2^22, d < 2^16
     const int q = (int)(((float)v + 0.5f) * inv);
@@ -148,7 +145,6 @@ __global__ __launch_bounds__(256, 2) void convT_bf16_kernel(const IgemmArgs a, c
                 h[0] = (elt_t)lo[0]; h[1] = (elt_t)lo[1]; h[2] = (elt_t)lo[2]; h[3] = (elt_t)lo[3];
                 h[4] = (elt_t)hi[0]; h[5] = (elt_t)hi[1]; h[6] = (elt_t)hi[2]; h[7] = (elt_t)hi[3];
             }
-            typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
             u32x4 u = __builtin_bit_cast(u32x4, h);
             const bool ok = avoff[i] != OOBV;             // a select, not a branch (rows past M: the affine of a zero is not zero)
 #pragma unroll
@@ -317,7 +313,6 @@ __global__ __launch_bounds__(256, 2) void convT_bf16_kernel(const IgemmArgs a, c
     const long o_left = (o_total - o_base) * 2;
     const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc((void*)((elt_t*)a.out0 + o_base), 0,
                                                                           (int)(o_left < 0x7fffffffL ? o_left : 0x7fffffffL), 0x00020000);
-    typedef __attribute__((ext_vector_type(4))) elt_t bf16x4;
     // this lane's pieces of a sub-tile: pixel rows r0 + 8 t (t = 0..3), channel group ch -- x advances by 8 per piece
     const int r0 = lane >> 3, ch = lane & 7;
     // BNS (round 4): da written here is the gradient at a BatchNorm + ReLU layer's output (the conv2 under this ConvTranspose); its
@@ -357,7 +352,7 @@ __global__ __launch_bounds__(256, 2) void convT_bf16_kernel(const IgemmArgs a, c
         // transposition, instead of one piece at a time between the stores -- hipcc kept each load behind the store before it
         // (it cannot tell the resources apart) and every piece waited out a memory round trip of its own (16 per wave and tile).
         // (Issued one sub-tile further ahead -- 24 pieces in flight, 256 registers -- measured the same.)
-        u32x4_t pb[4], pr[4], py[4];
+        u32x4 pb[4], pr[4], py[4];
         if constexpr (JOIN || BNS) {
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
@@ -400,7 +395,7 @@ __global__ __launch_bounds__(256, 2) void convT_bf16_kernel(const IgemmArgs a, c
                     v8[q] = (elt_t)((!j_mask || (float)r8[q] > 0.f) ? g : 0.f);
                 }
             }
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v8), ors, ok ? vo : OOBV, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v8), ors, ok ? vo : OOBV, 0, 0);
             if constexpr (BNS) {
                 const bf16x8 y8 = __builtin_bit_cast(bf16x8, py[t]);
 #pragma unroll

@@ -16,9 +16,6 @@
 namespace ustrun {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) elt_t bf16x8;
-typedef __attribute__((ext_vector_type(4))) elt_t bf16x4;
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
 constexpr int FTH = 8, FTW = 16, FHW = FTW + 2, FHP = (FTH + 2) * FHW;   // 10 x 18 patch
 constexpr int CMAX = 4;
@@ -311,8 +308,8 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const float* __re
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const char* base = dys + (r * FTW + lrow) * WRB + (j * 32 + lcol) * 2;
-                const bf16x4 lo = USTRUN_DS_READ_TR16((lds_bf16x4*)base);
-                const bf16x4 hi = USTRUN_DS_READ_TR16((lds_bf16x4*)(base + 4 * WRB));
+                const bf16x4 lo = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)base));
+                const bf16x4 hi = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + 4 * WRB)));
                 bf16x8 b;
                 b[0] = lo[0]; b[1] = lo[1]; b[2] = lo[2]; b[3] = lo[3]; b[4] = hi[0]; b[5] = hi[1]; b[6] = hi[2]; b[7] = hi[3];
                 acc[j] = USTRUN_MFMA_32x32x16(a, b, acc[j], 0, 0, 0);
@@ -345,7 +342,6 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_stream_kernel(const floa
                                                                       int H, int W, int xbytes, const elt_t* __restrict__ dy,
                                                                       int dybytes, float* __restrict__ partials, int strips, int segs,
                                                                       int seg_rows, int items) {
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     __shared__ __attribute__((aligned(16))) char dys[4 * 2 * FTW * WRB > 4 * 32 * 64 * 4 ? 4 * 2 * FTW * WRB : 4 * 32 * 64 * 4];
     float (*accs)[32][64] = (float (*)[32][64])dys;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -417,8 +413,8 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_stream_kernel(const floa
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const char* base = sl + lrow * WRB + (j * 32 + lcol) * 2;
-                const bf16x4 lo = USTRUN_DS_READ_TR16((lds_bf16x4*)base);
-                const bf16x4 hi = USTRUN_DS_READ_TR16((lds_bf16x4*)(base + 4 * WRB));
+                const bf16x4 lo = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)base));
+                const bf16x4 hi = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + 4 * WRB)));
                 bf16x8 b;
                 b[0] = lo[0]; b[1] = lo[1]; b[2] = lo[2]; b[3] = lo[3]; b[4] = hi[0]; b[5] = hi[1]; b[6] = hi[2]; b[7] = hi[3];
                 acc[j] = USTRUN_MFMA_32x32x16(a, b, acc[j], 0, 0, 0);
@@ -455,10 +451,6 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_stream_x3_kernel(const f
                                                                          int H, int W, int xbytes, const float* __restrict__ dy,
                                                                          int dybytes, float* __restrict__ partials, int strips, int segs,
                                                                          int seg_rows, int items) {
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-    typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-    typedef __attribute__((ext_vector_type(8))) __bf16 b16x8;
-    typedef __attribute__((ext_vector_type(4))) __bf16 b16x4;
     constexpr int SLOT = 3 * FTW * WRB;                                // three planes of [16 px][WRB]
     extern __shared__ __attribute__((aligned(16))) char dys[];         // 4 waves x 2 slots (>= 4 x 32 x 64 floats for the final sum)
     float (*accs)[32][64] = (float (*)[32][64])dys;
@@ -545,8 +537,8 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_stream_x3_kernel(const f
 #pragma unroll
                 for (int p = 0; p < 3; ++p) {
                     const char* base = sl + p * FTW * WRB + lrow * WRB + (j * 32 + lcol) * 2;
-                    const b16x4 lo = __builtin_bit_cast(b16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((ustrun_lds_s16x4*)base));
-                    const b16x4 hi = __builtin_bit_cast(b16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((ustrun_lds_s16x4*)(base + 4 * WRB)));
+                    const b16x4 lo = __builtin_bit_cast(b16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)base));
+                    const b16x4 hi = __builtin_bit_cast(b16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + 4 * WRB)));
                     b[p][0] = lo[0]; b[p][1] = lo[1]; b[p][2] = lo[2]; b[p][3] = lo[3];
                     b[p][4] = hi[0]; b[p][5] = hi[1]; b[p][6] = hi[2]; b[p][7] = hi[3];
                 }
@@ -741,7 +733,7 @@ __global__ __launch_bounds__(256, 3) void conv_first_fwd_stream_kernel(const flo
                 // wait state between a 128-bit buffer store and a VALU write of its data registers -- an SI-era rule -- and on gfx950,
                 // with the store pipe saturated, the store then ships the overwritten dword for the last lanes of each 16:
                 // 6e-6 of the outputs in the no-statistics build, none in the build whose statistics code sits in between)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v8), ry, ok ? ((oy * W + ox) * 64 + ch * 8) * 2 : OOB, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v8), ry, ok ? ((oy * W + ox) * 64 + ch * 8) * 2 : OOB, 0, 0);
                 if constexpr (STAT) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {

@@ -31,7 +31,6 @@ template <int ESZ, int CIN>
 __global__ __launch_bounds__(256) void conv_first_dgrad_kernel(const void* __restrict__ dy, const float* __restrict__ w,
                                                               int H, int W, int Cout, float* __restrict__ dx,
                                                               int tiles_x, int tiles_y) {
-    typedef __attribute__((ext_vector_type(4))) elt_t e16x4;
     __shared__ __attribute__((aligned(16))) char tile[DTILE];                   // later: the waves' sums [4][CIN][256]
     __shared__ __attribute__((aligned(16))) float wl[9 * CIN][DCH];
     static_assert(DTILE >= 4 * CIN * DT * DT * 4, "the final sum lives in the tile's memory");
@@ -65,7 +64,7 @@ __global__ __launch_bounds__(256) void conv_first_dgrad_kernel(const void* __res
                 if (ESZ == 4) {
                     v[i] = *(const f32x4*)((const float*)dy + o);
                 } else {
-                    const e16x4 h = *(const e16x4*)((const elt_t*)dy + o);
+                    const bf16x4 h = *(const bf16x4*)((const elt_t*)dy + o);
                     v[i] = (f32x4){(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
                 }
             }

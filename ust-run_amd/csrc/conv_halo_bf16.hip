@@ -17,10 +17,6 @@
 namespace ustrun {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) elt_t bf16x8;
-typedef __attribute__((ext_vector_type(4))) elt_t bf16x4;
-typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
 
 
 __device__ __attribute__((aligned(16))) const unsigned g_zero16[4] = {0u, 0u, 0u, 0u};   // source of padding pixels
@@ -255,7 +251,6 @@ __global__ __launch_bounds__(256, (TH * TW * BN >= 512 * 64 && BN == 64 ? 1 : 2)
             hi[q] = __builtin_amdgcn_fmed3f(hi[q], a_floor, __builtin_inff());
         }
     };
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     auto xform8 = [&](const bf16x8* r, bool inimg) {      // NP raw pieces -> one activated (pooled) bf16 group; no branches
         f32x4 lo, hi;
         act8(r[0], lo, hi);
@@ -688,8 +683,6 @@ __global__ __launch_bounds__(256, (TH * TW * BN >= 512 * 64 && BN == 64 ? 1 : 2)
     // sub-tile at a time through its own LDS scratch (rows padded to 144 B: the two half-waves hit disjoint
     // banks) and writes 16 bytes per lane, 128 contiguous bytes per pixel.
     const int C1 = a.Cout - a.C0;
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
-    typedef __attribute__((ext_vector_type(2))) elt_t bf16x2;
     f32x2 s1v[2] = {{0.f, 0.f}, {0.f, 0.f}}, s2v[2] = {{0.f, 0.f}, {0.f, 0.f}};    // two pixel rows at a time (packed f32 math)
     float s1p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, s2p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // M16: from the stored pieces
     auto stat_piece = [&](const bf16x8 v8, bool ok) {      // the lane's 8 channels (lane & 7) of one pixel: statistics see the stored values

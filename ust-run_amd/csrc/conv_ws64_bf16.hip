@@ -26,10 +26,6 @@
 namespace ustrun {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) elt_t bf16x8;
-typedef __attribute__((ext_vector_type(4))) elt_t bf16x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 constexpr int TW = 32, HW = TW + 2;
 constexpr int PITCH = 144;                     // ring pixel: 64 channels + 16 B pad (conflict-free ds_read_b128 at any tap)

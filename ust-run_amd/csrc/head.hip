@@ -61,7 +61,6 @@ __global__ __launch_bounds__(256) void head_fwd_bf16_kernel(const elt_t* __restr
                                                            const float* __restrict__ shift, long npix, int HW, int C, int G,
                                                            const float* __restrict__ w, const float* __restrict__ bias,
                                                            float* __restrict__ logits) {
-    typedef __attribute__((ext_vector_type(8))) elt_t bf16x8;
     const int g = threadIdx.x % G, pl = threadIdx.x / G, PPB = 256 / G;
     float sc[8], sh[8], wk[K][8];
     {   // the lane's constants as 16-byte loads, all issued together (they were 8 x (2 + K) dependent 4-byte loads: a few
@@ -129,7 +128,6 @@ __global__ __launch_bounds__(256) void head_fwd_bf16_g8_kernel(const elt_t* __re
                                                               const float* __restrict__ shift, long npix, int HW,
                                                               const float* __restrict__ w, const float* __restrict__ bias,
                                                               float* __restrict__ logits) {
-    typedef __attribute__((ext_vector_type(8))) elt_t bf16x8;
     constexpr int C = 64, PPB = 32, U = 8, KP = K <= 1 ? 1 : (K <= 2 ? 2 : 4);
     const int g = threadIdx.x & 7, pl = threadIdx.x >> 3;
     float sc[8], sh[8], wk[KP][8];

@@ -9,8 +9,6 @@
 namespace ustrun {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) elt_t bf16x8;
-typedef __attribute__((ext_vector_type(4))) elt_t bf16x4;
 
 struct RowInfo { int n; int yx; };
 
@@ -308,7 +306,6 @@ __global__ __launch_bounds__(256) void pack_bf16_multi_kernel(const PackJobs job
     // 16-byte pieces that add up to whole 128-byte (forward) and 1 KB (input-gradient) runs.  The element-per-thread
     // path below wrote 2-byte pieces 16 bytes apart: 1.3 GB of HBM traffic for 248 MB of weights.
     if (!j.transposed_src && taps == 9 && Cin % 64 == 0 && Cout % 8 == 0 && wd) {
-        typedef __attribute__((ext_vector_type(8))) elt_t bf16x8;
         __shared__ elt_t t[8][64 * 9 + 2];                 // [co][ci*9 + tap] (+2: rows start 4 bytes apart in the banks)
         const int Ki = Cin / 8, Ko = Cout / 8, tiles_ci = Cin / 64, ntile = Ko * tiles_ci;
         for (int tile = blockIdx.x; tile < ntile; tile += gridDim.x) {

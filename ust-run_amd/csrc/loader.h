@@ -6,12 +6,11 @@
 
 namespace ustrun {
 
-typedef __attribute__((ext_vector_type(4))) elt_t bf16x4_t;
 
 // element-type-agnostic accessors: `base` is the tensor base, idx an ELEMENT index, esz 4 (f32) or 2 (bf16)
 __device__ __forceinline__ f32x4 ld4(const float* base, long idx, int esz) {
     if (esz == 4) return *(const f32x4*)(base + idx);
-    const bf16x4_t h = *(const bf16x4_t*)((const elt_t*)base + idx);
+    const bf16x4 h = *(const bf16x4*)((const elt_t*)base + idx);
     return (f32x4){(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
 }
 __device__ __forceinline__ float ld1(const float* base, long idx, int esz) {
@@ -19,9 +18,9 @@ __device__ __forceinline__ float ld1(const float* base, long idx, int esz) {
 }
 __device__ __forceinline__ void st4(float* base, long idx, f32x4 v, int esz) {
     if (esz == 4) { *(f32x4*)(base + idx) = v; return; }
-    bf16x4_t h;
+    bf16x4 h;
     h[0] = (elt_t)v[0]; h[1] = (elt_t)v[1]; h[2] = (elt_t)v[2]; h[3] = (elt_t)v[3];
-    *(bf16x4_t*)((elt_t*)base + idx) = h;
+    *(bf16x4*)((elt_t*)base + idx) = h;
 }
 __device__ __forceinline__ void st1(float* base, long idx, float v, int esz) {
     if (esz == 4) base[idx] = v; else ((elt_t*)base)[idx] = (elt_t)v;
@@ -34,16 +33,16 @@ __device__ __forceinline__ float rnd(float v, int esz) { return esz == 4 ? v : (
 template <int ESZ> __device__ __forceinline__ f32x4 ld4t(const float* base, long idx) {
     if constexpr (ESZ == 4) return *(const f32x4*)(base + idx);
     else {
-        const bf16x4_t h = *(const bf16x4_t*)((const elt_t*)base + idx);
+        const bf16x4 h = *(const bf16x4*)((const elt_t*)base + idx);
         return (f32x4){(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
     }
 }
 template <int ESZ> __device__ __forceinline__ void st4t(float* base, long idx, f32x4 v) {
     if constexpr (ESZ == 4) *(f32x4*)(base + idx) = v;
     else {
-        bf16x4_t h;
+        bf16x4 h;
         h[0] = (elt_t)v[0]; h[1] = (elt_t)v[1]; h[2] = (elt_t)v[2]; h[3] = (elt_t)v[3];
-        *(bf16x4_t*)((elt_t*)base + idx) = h;
+        *(bf16x4*)((elt_t*)base + idx) = h;
     }
 }
 template <int ESZ> __device__ __forceinline__ void st1t(float* base, long idx, float v) {

@@ -501,8 +501,6 @@ extern "C" int ustrun_aspp_gather(const float* z, int N, int h, int w, int K, in
 __global__ __launch_bounds__(256) void space_to_batch_kernel(const elt_t* __restrict__ x, const float* __restrict__ scale,
                                                              const float* __restrict__ shift, int relu, int N, int H, int W, int C, int r,
                                                              int Hs, int Ws, elt_t* __restrict__ out) {
-    typedef __attribute__((ext_vector_type(8))) elt_t v8;
-    typedef __attribute__((ext_vector_type(4))) unsigned u4;
     const int C8 = C / 8;
     const long total = (long)N * r * r * Hs * Ws * C8;
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
@@ -514,9 +512,9 @@ __global__ __launch_bounds__(256) void space_to_batch_kernel(const elt_t* __rest
         const int a = (int)(t % r);
         const int n = (int)(t / r);
         const int yy = i * r + a, xx = j * r + b;
-        u4 o = {0u, 0u, 0u, 0u};
+        u32x4 o = {0u, 0u, 0u, 0u};
         if (yy < H && xx < W) {
-            v8 v = *(const v8*)(x + (((long)n * H + yy) * W + xx) * C + c8 * 8);
+            bf16x8 v = *(const bf16x8*)(x + (((long)n * H + yy) * W + xx) * C + c8 * 8);
             if (scale) {
                 const f32x4 s0 = *(const f32x4*)(scale + c8 * 8), s1 = *(const f32x4*)(scale + c8 * 8 + 4);
                 const f32x4 b0 = *(const f32x4*)(shift + c8 * 8), b1 = *(const f32x4*)(shift + c8 * 8 + 4);
@@ -527,9 +525,9 @@ __global__ __launch_bounds__(256) void space_to_batch_kernel(const elt_t* __rest
                     v[q] = (elt_t)f;
                 }
             }
-            o = __builtin_bit_cast(u4, v);
+            o = __builtin_bit_cast(u32x4, v);
         }
-        *(u4*)(out + e * 8) = o;
+        *(u32x4*)(out + e * 8) = o;
     }
 }
 

@@ -296,6 +296,11 @@ int wgrad_plan(int nseg, int Cin, int Cout, int64_t M, int* ksplit, long* kchunk
     return 0;
 }
 
+// the kernel the calling thread's last weight gradient ran (ustrun_debug_last_wgrad_variant): every member of the family sets it
+thread_local int g_last_wgrad_variant = 0;
+int wgrad_last_variant() { return g_last_wgrad_variant; }
+void set_last_wgrad_variant(int v) { g_last_wgrad_variant = v; }
+
 int wgrad_launch(const WgradArgs& a, int dtype, hipStream_t st) {
     USTRUN_CHECK(dtype_ok(dtype), "wgrad: dtype %d not built", dtype);
     USTRUN_CHECK(a.M > 0 && a.Cin > 0 && a.Cout > 0, "wgrad: empty problem");

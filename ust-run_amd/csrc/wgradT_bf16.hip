@@ -5,8 +5,7 @@
 //
 // One GEMM over the low-resolution pixels m with the four taps folded into the COLUMN axis: a block owns
 // 128 ci x (4 taps x 32 co) columns and a contiguous range of pixels (split-K over space), 64 pixels per
-// stage, double-buffered.  Both operands stay pixel-major in LDS ([pixel][channel], 64-byte segments XORed by
-// the pixel index) and the fragments come from the transposing LDS read, as in wgrad_bf16.hip.  The activation
+// stage, double-buffered.  LDS layout, fragments and block order: see tn_gemm.h.  The activation
 // tile goes global -> registers -> [BatchNorm affine + ReLU, f32] -> bf16 -> LDS; the du tile is a pure copy and
 // is fetched by LDS-DMA (the swizzle is applied on the global side: every lane fetches the 16 bytes that belong
 // at its LDS position).  The du fragments are gathered so that the 32 accumulator lanes are (8 co) x (4 taps):
@@ -15,31 +14,12 @@
 // MFMA with an all-ones A fragment per du fragment, whose result is the column sum of du.
 #include "common.h"
 #include "loader.h"
+#include "tn_gemm.h"
 
 namespace ustrun {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) elt_t bf16x8;
-typedef __attribute__((ext_vector_type(4))) elt_t bf16x4;
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
-
 constexpr int TM = 128, TN = 128, KP = 64, RB = 256;   // tile, pixels per stage, LDS row pitch (bytes)
-
-// rows k0 + 8*(l>>5) + {0..3 | 4..7}, columns col0 + 16*((l>>4)&1) + 4*(l&3) .. +3, delivered column-major
-__device__ __forceinline__ bf16x8 tr_frag(const char* tile, int k0, int col0, int lane) {
-    const int q = (lane & 15) >> 2, p = lane & 3;
-    const int colb = (col0 + 16 * ((lane >> 4) & 1) + 4 * p) * 2;
-    const int r0 = k0 + 8 * (lane >> 5) + q, r1 = r0 + 4;      // r1 & 3 == r0 & 3
-    const int off = colb ^ ((r0 & 3) << 6);
-    const bf16x4 lo = USTRUN_DS_READ_TR16((lds_bf16x4*)(tile + r0 * RB + off));
-    const bf16x4 hi = USTRUN_DS_READ_TR16((lds_bf16x4*)(tile + r1 * RB + off));
-    bf16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-    return f;
-}
 
 // du fragment of 8-co group t: lane (q, p, g) reads row q, tap p, channels 8t + 4g .. +3 of the [tap][32 co] row,
 // so after the transpose lane 16g + 4*tap + c of the MFMA holds column (co = 8t + 4g + c, tap)
@@ -47,21 +27,7 @@ __device__ __forceinline__ bf16x8 tr_frag_du(const char* tile, int k0, int t, in
     const int q = (lane & 15) >> 2, p = lane & 3, g = (lane >> 4) & 1;
     const int r0 = k0 + 8 * (lane >> 5) + q, r1 = r0 + 4;
     const int off = ((p ^ (r0 & 3)) << 6) + 16 * t + 8 * g;
-    const bf16x4 lo = USTRUN_DS_READ_TR16((lds_bf16x4*)(tile + r0 * RB + off));
-    const bf16x4 hi = USTRUN_DS_READ_TR16((lds_bf16x4*)(tile + r1 * RB + off));
-    bf16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-    return f;
-}
-
-__device__ __forceinline__ int wrap_add(int x, int inc, int W, float invW) {   // (x + inc) mod W, x < W < 2^15, inc <= 64
-    const int v = x + inc;
-    const int q = (int)(((float)v + 0.5f) * invW);
-    int r = v - q * W;
-    if (r < 0) r += W;
-    if (r >= W) r -= W;
-    return r;
+    return tr_pair(tile + r0 * RB + off, tile + r1 * RB + off);
 }
 
 // grid = (ci tiles * column tiles, ksplit)
@@ -73,15 +39,9 @@ __global__ __launch_bounds__(256, 2) void wgradT_bf16_kernel(const WgradArgs a, 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform: LDS-DMA bases and role tests stay scalar
     const int wm = wave >> 1, wn = wave & 1;
-    // XCD-aware order (1-D grid, workgroups go round-robin over the 8 XCDs): every XCD takes a contiguous range of the
-    // (slice-major, tile-minor) order, so all (ci, column) tiles of one pixel slice share one XCD's L2: the slice's
-    // activations and du come from HBM once instead of once per tile (the kernel is HBM-bound: 5.7 TB/s measured).
+    // XCD order: all (ci, column) tiles of one pixel slice share one XCD's L2 (the kernel is HBM-bound: 5.7 TB/s measured)
     const int nblk = gridDim.x, tiles = nblk / a.ksplit;
-    int lin;
-    {
-        const int q = nblk / 8, r = nblk % 8, xcd = blockIdx.x % 8, jj = blockIdx.x / 8;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + jj;
-    }
+    const int lin = xcd_linear(blockIdx.x, nblk);
     const int ks = lin / tiles, tile = lin - ks * tiles;
     const int mtile = tile / ntn, ntile = tile % ntn;
     const int ci0 = mtile * TM, co0 = ntile * 32;
@@ -195,8 +155,8 @@ __global__ __launch_bounds__(256, 2) void wgradT_bf16_kernel(const WgradArgs a, 
         const char* Bt = Bs + buf * (KP * RB);
 #pragma unroll
         for (int kk = 0; kk < KP / 16; ++kk) {
-            const bf16x8 a0 = tr_frag(At, kk * 16, wm * 64, lane);
-            const bf16x8 a1 = tr_frag(At, kk * 16, wm * 64 + 32, lane);
+            const bf16x8 a0 = tr_frag<RB>(At, kk * 16, wm * 64, lane);
+            const bf16x8 a1 = tr_frag<RB>(At, kk * 16, wm * 64 + 32, lane);
             const bf16x8 b0 = tr_frag_du(Bt, kk * 16, 2 * wn, lane);
             const bf16x8 b1 = tr_frag_du(Bt, kk * 16, 2 * wn + 1, lane);
             if (do_bias) {
@@ -266,11 +226,10 @@ __global__ __launch_bounds__(256, 2) void wgradT_bf16_kernel(const WgradArgs a, 
 constexpr int KP2 = 32, BRB2 = 512;
 // the bias gradient = column sums of du: each lane adds the eight K entries of its column with four packed dot products against
 // (1, 1) -- four registers and 16 VALU instructions per 16 pixels where an all-ones MFMA per fragment took 64 registers
-typedef __attribute__((ext_vector_type(2))) elt_t elt2_t;
 #ifdef USTRUN_ELT_F16
-#define USTRUN_DOT2_ONES(pair, acc) __builtin_amdgcn_fdot2(pair, (elt2_t){(elt_t)1.f, (elt_t)1.f}, acc, false)
+#define USTRUN_DOT2_ONES(pair, acc) __builtin_amdgcn_fdot2(pair, (bf16x2){(elt_t)1.f, (elt_t)1.f}, acc, false)
 #else
-#define USTRUN_DOT2_ONES(pair, acc) __builtin_amdgcn_fdot2_f32_bf16(pair, (elt2_t){(elt_t)1.f, (elt_t)1.f}, acc, false)
+#define USTRUN_DOT2_ONES(pair, acc) __builtin_amdgcn_fdot2_f32_bf16(pair, (bf16x2){(elt_t)1.f, (elt_t)1.f}, acc, false)
 #endif
 template <int TM> struct T2 {
     static constexpr int ARB = TM * 2;                       // activation row pitch (bytes)
@@ -300,17 +259,12 @@ __global__ __launch_bounds__(2 * TM, 2) void wgradT2_bf16_kernel(const WgradArgs
     typedef T2<TM> G;
     constexpr int ARB = G::ARB, ATILE = G::ATILE, STAGE = G::STAGE, AIT = G::AIT, BIT = G::BIT, WN = G::WN, NT = G::NT, NTH = G::NTH;
     constexpr int OOB = (int)0x80000000;
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // 3 x {activation [32 px][TM], du [32 px][2 halves][4 taps][32 co]}
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int nblk = gridDim.x, tiles = nblk / a.ksplit;          // XCD-contiguous (slice-major) order, as above
-    int lin;
-    {
-        const int q = nblk / 8, r = nblk % 8, xcd = blockIdx.x % 8, jj = blockIdx.x / 8;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + jj;
-    }
+    const int lin = xcd_linear(blockIdx.x, nblk);
     const int ks = lin / tiles, tile = lin - ks * tiles;
     const int mtile = tile / ntn, ntile = tile % ntn;
     const int ci0 = mtile * TM, co0 = ntile * 64;
@@ -418,22 +372,10 @@ __global__ __launch_bounds__(2 * TM, 2) void wgradT2_bf16_kernel(const WgradArgs
     const int half = wn, t0 = 0;
     const int bbase = ATILE + frow * BRB2 + 256 * half + ((fp ^ fq) << 6) + 8 * fg + 16 * t0;
     auto fragA = [&](const char* st, int i, int k0) {
-        const char* p = st + abase[i] + k0 * ARB;
-        const bf16x4 lo = USTRUN_DS_READ_TR16((lds_bf16x4*)p);
-        const bf16x4 hi = USTRUN_DS_READ_TR16((lds_bf16x4*)(p + 4 * ARB));
-        bf16x8 f;
-        f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-        f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-        return f;
+        return tr_frag_rows<ARB>(st + abase[i], k0);
     };
     auto fragB = [&](const char* st, int t, int k0) {
-        const char* p = st + bbase + 16 * t + k0 * BRB2;
-        const bf16x4 lo = USTRUN_DS_READ_TR16((lds_bf16x4*)p);
-        const bf16x4 hi = USTRUN_DS_READ_TR16((lds_bf16x4*)(p + 4 * BRB2));
-        bf16x8 f;
-        f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-        f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-        return f;
+        return tr_frag_rows<BRB2>(st + bbase + 16 * t, k0);
     };
 
     auto wait_all_but_one_stage = [&]() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(AIT + BIT) : "memory"); };
@@ -465,7 +407,7 @@ __global__ __launch_bounds__(2 * TM, 2) void wgradT2_bf16_kernel(const WgradArgs
 #pragma unroll
                 for (int j = 0; j < NT; ++j)
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) accb[j] = USTRUN_DOT2_ONES(((elt2_t){bf[j][2 * q], bf[j][2 * q + 1]}), accb[j]);
+                    for (int q = 0; q < 4; ++q) accb[j] = USTRUN_DOT2_ONES(((bf16x2){bf[j][2 * q], bf[j][2 * q + 1]}), accb[j]);
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i)

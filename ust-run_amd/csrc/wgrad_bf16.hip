@@ -1,37 +1,12 @@
 // wgrad_bf16.hip -- the weight-gradient "TN" GEMM of wgrad.hip on the bf16 matrix cores.
-// The contraction runs over pixels while both operands are stored pixel-major (NHWC), so each lane
-// needs 8 consecutive PIXELS of one channel: the LDS tiles keep the natural [pixel][channel] layout
-// (coalesced fills, 8-byte stores) and the fragments are fetched with the transposing LDS read
-// ds_read_b64_tr_b16 (4 rows x 16 columns per 16-lane group, delivered column-major).
+// The contraction runs over pixels while both operands are stored pixel-major (NHWC): the LDS tiles keep the natural
+// [pixel][channel] layout (coalesced fills, 8-byte stores) and the fragments come from the transposing LDS read -- see tn_gemm.h.
 #include "common.h"
 #include "loader.h"
+#include "tn_gemm.h"
 
 namespace ustrun {
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) elt_t bf16x8;
-typedef __attribute__((ext_vector_type(4))) elt_t bf16x4;
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-
-
-// 64-byte segments of a row are XOR-permuted by the row index so that the 4 rows of a transposed
-// read fall on different bank segments
-template <int RB> __device__ __forceinline__ int seg_swz(int row) { return RB >= 256 ? (row & 3) : ((row >> 1) & 1); }
-
-template <int RB> __device__ __forceinline__ bf16x8 tr_frag(const char* tile, int k0, int col0, int lane) {
-    // lane l of the wave: rows k0 + 8*(l>>5) + {0..3 | 4..7}, columns col0 + 16*((l>>4)&1) + ...
-    const int q = (lane & 15) >> 2, p = lane & 3;
-    const int colb = (col0 + 16 * ((lane >> 4) & 1) + 4 * p) * 2;
-    const int r0 = k0 + 8 * (lane >> 5) + q, r1 = r0 + 4;
-    const char* a0 = tile + r0 * RB + (colb ^ (seg_swz<RB>(r0) << 6));
-    const char* a1 = tile + r1 * RB + (colb ^ (seg_swz<RB>(r1) << 6));
-    const bf16x4 lo = USTRUN_DS_READ_TR16((lds_bf16x4*)a0);
-    const bf16x4 hi = USTRUN_DS_READ_TR16((lds_bf16x4*)a1);
-    bf16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-    return f;
-}
 
 template <int TM, int TN, bool POOL>
 __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const WgradArgs a, const int mtn, const int ntn) {

@@ -9,20 +9,15 @@
 // page).  Both are pixel-major with 192-byte rows (128 B of channels + 64 B pad: the 4 rows of a transposing
 // read fall on disjoint bank quarters and every fragment address is base + immediate).  Each wave owns a 32x32
 // (ci,co) quadrant with nine accumulators: per 16-pixel row one activation fragment and nine shifted dY fragments
-// (ds_read_b64_tr_b16), nine MFMAs.  Tiles are double-buffered: one barrier per tile.  The block walks a range of
+// (tr_frag_rows, tn_gemm.h), nine MFMAs.  Tiles are double-buffered: one barrier per tile.  The block walks a range of
 // tiles (split-K over space) and writes one f32 slab already in the torch [Cout][Cin][3][3] layout, summed in
 // fixed order by a plain streaming reduce.
 #include "common.h"
 #include "loader.h"
+#include "tn_gemm.h"
 
 namespace ustrun {
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) elt_t bf16x8;
-typedef __attribute__((ext_vector_type(4))) elt_t bf16x4;
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
 
 constexpr int TH = 4, TW = 16, HW2 = TW + 2, HP = (TH + 2) * HW2;   // 108 halo pixels
 constexpr int RB = 192;                          // LDS row pitch
@@ -32,16 +27,6 @@ constexpr int DIT = (DSLOTS + 255) / 256;        // dY DMA items per thread per 
 constexpr int ATILE = TH * TW * RB, DTILE = DSLOTS * 16;
 
 __device__ __attribute__((aligned(16))) const unsigned g_zero16w[4] = {0u, 0u, 0u, 0u};
-
-// lane_base = per-lane byte offset ((8*(l>>5) + q) * RB + column bytes), k0 = first pixel row of the fragment
-__device__ __forceinline__ bf16x8 tr_frag(const char* lane_base, int k0) {
-    const bf16x4 lo = USTRUN_DS_READ_TR16((lds_bf16x4*)(lane_base + k0 * RB));
-    const bf16x4 hi = USTRUN_DS_READ_TR16((lds_bf16x4*)(lane_base + (k0 + 4) * RB));
-    bf16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-    return f;
-}
 
 // grid = (ci tiles * co tiles, ksplit); tiles_per = spatial tiles per split
 template <bool POOL>
@@ -199,12 +184,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradArgs
         // every dY fragment (patch row pr, column shift kw) feeds up to three taps: load it once, use it at once
         bf16x8 af[TH];
 #pragma unroll
-        for (int r = 0; r < TH; ++r) af[r] = tr_frag(Ab, r * TW);
+        for (int r = 0; r < TH; ++r) af[r] = tr_frag_rows<RB>(Ab, r * TW);
 #pragma unroll
         for (int pr = 0; pr < TH + 2; ++pr) {
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
-                const bf16x8 b = tr_frag(Db, pr * HW2 + 2 - kw);
+                const bf16x8 b = tr_frag_rows<RB>(Db, pr * HW2 + 2 - kw);
 #pragma unroll
                 for (int kh = 0; kh < 3; ++kh) {      // tap (kh,kw) pairs pixel row r with dY row r + 2 - kh of the patch
                     const int r = pr + kh - 2;
@@ -260,15 +245,6 @@ __device__ __forceinline__ void dma16(const void* gsrc, const char* lds_wave_bas
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(gsrc), "s"(m) : "memory", "m0");
 }
 
-__device__ __forceinline__ bf16x8 tr_frag3(const char* lane_base, int k0) {
-    const bf16x4 lo = USTRUN_DS_READ_TR16((lds_bf16x4*)(lane_base + k0 * RB3));
-    const bf16x4 hi = USTRUN_DS_READ_TR16((lds_bf16x4*)(lane_base + (k0 + 4) * RB3));
-    bf16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-    return f;
-}
-
 template <int T3>
 __global__ __launch_bounds__(256, 2) void wgrad_halo3_bf16_kernel(const WgradArgs a, const int ntn, const int tiles_x,
                                                                   const int tiles_y, const int tiles_per) {
@@ -279,16 +255,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo3_bf16_kernel(const WgradArg
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform: LDS-DMA bases and role tests stay scalar
     const int wi = wave >> 1, wj = wave & 1;
-    // XCD-aware order (1-D grid, workgroups go round-robin over the 8 XCDs): every XCD takes a contiguous range of the
-    // (slice-major, pair-minor) order, so the (ci, co) pairs of one spatial slice run on ONE XCD: the slice's activation
-    // and dY tiles come from HBM once and the other pairs re-read them from that XCD's L2 -- with the natural order the
-    // Cin/64 x Cout/64 re-reads were spread over all eight L2s.
+    // XCD order (tn_gemm.h): the (ci, co) pairs of one spatial slice run on one XCD
     const int nblk = gridDim.x, pairs = nblk / a.ksplit;
-    int lin;
-    {
-        const int q = nblk / 8, r = nblk % 8, xcd = blockIdx.x % 8, j = blockIdx.x / 8;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int lin = xcd_linear(blockIdx.x, nblk);
     const int slice = lin / pairs, pair = lin - slice * pairs;
     const int mtile = pair / ntn, ntile = pair % ntn;
     const int ci0 = mtile * 64, co0 = ntile * 64;
@@ -371,7 +340,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo3_bf16_kernel(const WgradArg
         if (!xf) return;
         // all items read first (one LDS round trip), selects instead of per-item branches (items outside the source
         // hold zeros and must stay zero: relu(shift) is not)
-        typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
         const float floor_ = S.relu ? 0.f : -__builtin_inff();
 #pragma unroll
         for (int i0 = 0; i0 < A3IT; i0 += 2) {              // two items per LDS round trip (four would spill)
@@ -443,14 +411,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo3_bf16_kernel(const WgradArg
             const char* Ab = st[0] + abase;
             bf16x8 af[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) af[r] = tr_frag3(Ab, (4 * h + r) * TW);
+            for (int r = 0; r < 4; ++r) af[r] = tr_frag_rows<RB3>(Ab, (4 * h + r) * TW);
             // the three dY fragments of the next patch row are in flight while this row's MFMAs run (one LDS round trip
             // per row instead of one per fragment)
             bf16x8 bq[2][3];
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
                 const int k0 = 4 * h * HW2 + 2 - kw;
-                bq[0][kw] = tr_frag3(st[0] + dbase4[k0 & 3], k0);
+                bq[0][kw] = tr_frag_rows<RB3>(st[0] + dbase4[k0 & 3], k0);
             }
 #pragma unroll
             for (int pr = 0; pr < 6; ++pr) {
@@ -458,7 +426,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo3_bf16_kernel(const WgradArg
 #pragma unroll
                     for (int kw = 0; kw < 3; ++kw) {
                         const int k0 = (4 * h + pr + 1) * HW2 + 2 - kw;
-                        bq[(pr + 1) & 1][kw] = tr_frag3(st[0] + dbase4[k0 & 3], k0);
+                        bq[(pr + 1) & 1][kw] = tr_frag_rows<RB3>(st[0] + dbase4[k0 & 3], k0);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -522,18 +490,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo4_bf16_kernel(const WgradArg
     constexpr int A3IT = G::AIT, D3IT = G::DIT, D3SLOTS = G::DSLOTS, A3TILE = G::ATILE, STAGE3 = G::STAGE, NBUF = G::NBUF;
     constexpr int HPX = G::HPX;
     constexpr int OOB = (int)0x80000000;
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // NBUF x {activation tile [T3*16 px][128 B], dY patch [HPX px][128 B]}
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wi = wave >> 1, wj = wave & 1;
-    const int nblk = gridDim.x, pairs = nblk / a.ksplit;          // XCD-contiguous slices, as above
-    int lin;
-    {
-        const int q = nblk / 8, r = nblk % 8, xcd = blockIdx.x % 8, j = blockIdx.x / 8;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int nblk = gridDim.x, pairs = nblk / a.ksplit;
+    const int lin = xcd_linear(blockIdx.x, nblk);
     const int slice = lin / pairs, pair = lin - slice * pairs;
     const int mtile = pair / ntn, ntile = pair % ntn;
     const int ci0 = mtile * 64, co0 = ntile * 64;
@@ -723,12 +685,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo4_bf16_kernel(const WgradArg
             const char* Ab = st[0] + abase;
             bf16x8 af[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) af[r] = tr_frag3(Ab, (4 * h + r) * TW);
+            for (int r = 0; r < 4; ++r) af[r] = tr_frag_rows<RB3>(Ab, (4 * h + r) * TW);
             bf16x8 bq[2][3];
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
                 const int k0 = 4 * h * HW2 + 2 - kw;
-                bq[0][kw] = tr_frag3(st[0] + dbase4[k0 & 3], k0);
+                bq[0][kw] = tr_frag_rows<RB3>(st[0] + dbase4[k0 & 3], k0);
             }
 #pragma unroll
             for (int pr = 0; pr < 6; ++pr) {
@@ -736,7 +698,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo4_bf16_kernel(const WgradArg
 #pragma unroll
                     for (int kw = 0; kw < 3; ++kw) {
                         const int k0 = (4 * h + pr + 1) * HW2 + 2 - kw;
-                        bq[(pr + 1) & 1][kw] = tr_frag3(st[0] + dbase4[k0 & 3], k0);
+                        bq[(pr + 1) & 1][kw] = tr_frag_rows<RB3>(st[0] + dbase4[k0 & 3], k0);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -808,19 +770,13 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_pp_bf16_kernel(const WgradA
     constexpr int A3IT = G::AIT, D3IT = G::DIT, D3SLOTS = G::DSLOTS, A3TILE = G::ATILE, STAGE3 = G::STAGE;
     constexpr int HPX = G::HPX;
     constexpr int OOB = (int)0x80000000;
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 groups x 2 x {activation tile, dY patch}
     const int lane = threadIdx.x & 63, gt = threadIdx.x & 255;
     const int wave8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = wave8 >> 2, wave = wave8 & 3;
     const int wi = wave >> 1, wj = wave & 1;
     const int nblk = gridDim.x, pairs = nblk / a.ksplit;
-    int lin;
-    {
-        const int q = nblk / 8, r = nblk % 8, xcd = blockIdx.x % 8, j = blockIdx.x / 8;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int lin = xcd_linear(blockIdx.x, nblk);
     const int slice = lin / pairs, pair = lin - slice * pairs;
     const int mtile = pair / ntn, ntile = pair % ntn;
     const int ci0 = mtile * 64, co0 = ntile * 64;
@@ -982,12 +938,12 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_pp_bf16_kernel(const WgradA
             const char* Ab = stage + abase;
             bf16x8 af[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) af[r] = tr_frag3(Ab, (4 * h + r) * TW);
+            for (int r = 0; r < 4; ++r) af[r] = tr_frag_rows<RB3>(Ab, (4 * h + r) * TW);
             bf16x8 bq[2][3];
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
                 const int k0 = 4 * h * HW2 + 2 - kw;
-                bq[0][kw] = tr_frag3(stage + dbase4[k0 & 3], k0);
+                bq[0][kw] = tr_frag_rows<RB3>(stage + dbase4[k0 & 3], k0);
             }
 #pragma unroll
             for (int pr = 0; pr < 6; ++pr) {
@@ -995,7 +951,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_pp_bf16_kernel(const WgradA
 #pragma unroll
                     for (int kw = 0; kw < 3; ++kw) {
                         const int k0 = (4 * h + pr + 1) * HW2 + 2 - kw;
-                        bq[(pr + 1) & 1][kw] = tr_frag3(stage + dbase4[k0 & 3], k0);
+                        bq[(pr + 1) & 1][kw] = tr_frag_rows<RB3>(stage + dbase4[k0 & 3], k0);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);

@@ -3,54 +3,21 @@
 //
 //   dW[tap][ci][co] = sum_p act(x[stride * p + dilation * (tap - k/2)][ci]) * dy[p][co]          p over the output grid
 //
-// A "TN" GEMM over pixels whose operands are both pixel-major in HBM.  A block owns 128 (or 64) ci x 128 (or 64) co of one tap and a
-// contiguous range of output pixels (split-K over space), 64 pixels per stage, double-buffered; the tiles stay
-// [pixel][channel] in LDS (256-byte rows, 64-byte segments XORed by the pixel index) and the MFMA fragments come from the
-// transposing LDS read (ds_read_b64_tr_b16), as in wgradT_bf16.hip.  The activation tile goes global -> registers ->
-// [BatchNorm affine + ReLU in f32, zero outside the image] -> bf16 -> LDS, the dy tile global -> registers -> LDS: the loads
-// of stage s+1 are issued before the MFMAs of stage s and written to the other buffer after them.  The taps of one pixel range run next to each other on one XCD (block order below),
-// so the nine shifted reads of x and the nine reads of dy meet in that XCD's L2.  Partial slabs [ksplit][tap][ci][co] f32 are
-// summed in a fixed order by reduce_partials (1x1: slabs already in the torch layout, see SWAP).
+// The shared parts of the family (pixel-major LDS tiles, swizzle, transposing read, XCD block order, index helpers, split-K plan)
+// are in tn_gemm.h.  Here a block owns 128 (or 64) ci x 128 (or 64) co of one tap and a contiguous range of output pixels, 64 pixels
+// per stage, double-buffered.  The activation tile goes global -> registers -> [BatchNorm affine + ReLU in f32, zero outside the
+// image] -> bf16 -> LDS, the dy tile global -> registers -> LDS: the loads of stage s+1 are issued before the MFMAs of stage s and
+// written to the other buffer after them.  The taps of one pixel range run next to each other on one XCD, so the nine shifted reads
+// of x and the nine reads of dy meet in that XCD's L2.  Partial slabs [ksplit][tap][ci][co] f32 are summed in a fixed order by
+// reduce_partials (1x1: slabs already in the torch layout, see SWAP).
 #include "common.h"
 #include "loader.h"
+#include "tn_gemm.h"
 
 namespace ustrun {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) elt_t bf16x8;
-typedef __attribute__((ext_vector_type(4))) elt_t bf16x4;
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
-
 constexpr int KP = 64;   // pixels per stage; tiles are TM ci x TN co (128 or 64 each), LDS rows TM*2 / TN*2 bytes
-
-// 64-byte segments of a row are XOR-permuted by the row index so that the 4 rows of a transposed read fall on different bank
-// segments (256-byte rows: 4 segments, row & 3; 128-byte rows: 2 segments, (row >> 1) & 1)
-template <int RB> __device__ __forceinline__ int seg_swz(int row) { return RB >= 256 ? (row & 3) : ((row >> 1) & 1); }
-
-// rows k0 + 8*(l>>5) + {0..3 | 4..7}, columns col0 + 16*((l>>4)&1) + 4*(l&3) .. +3, delivered column-major
-template <int RB> __device__ __forceinline__ bf16x8 tr_frag(const char* tile, int k0, int col0, int lane) {
-    const int q = (lane & 15) >> 2, p = lane & 3;
-    const int colb = (col0 + 16 * ((lane >> 4) & 1) + 4 * p) * 2;
-    const int r0 = k0 + 8 * (lane >> 5) + q, r1 = r0 + 4;
-    const bf16x4 lo = USTRUN_DS_READ_TR16((lds_bf16x4*)(tile + r0 * RB + (colb ^ (seg_swz<RB>(r0) << 6))));
-    const bf16x4 hi = USTRUN_DS_READ_TR16((lds_bf16x4*)(tile + r1 * RB + (colb ^ (seg_swz<RB>(r1) << 6))));
-    bf16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-    return f;
-}
-
-// v / d and the remainder for 0 <= v < 2^24 through the float reciprocal (two fix-up steps make it exact)
-__device__ __forceinline__ int fdiv(int v, int d, float invd, int& rem) {
-    int q = (int)(((float)v + 0.5f) * invd);
-    int r = v - q * d;
-    if (r < 0) { --q; r += d; }
-    if (r >= d) { ++q; r -= d; }
-    rem = r;
-    return q;
-}
 
 // grid = (ci tiles * co tiles * taps * ksplit)
 // SWAP (1x1 convolutions): the MFMA operands trade places, D rows are co and its lanes ci, so the slab comes out as [co][ci] --
@@ -71,14 +38,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_tap_bf16_kernel(const WgradArgs 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    // XCD-aware order (1-D grid, workgroups go round-robin over the 8 XCDs): every XCD takes a contiguous range of the
-    // (slice-major, tile-minor) order, so all (tap, ci, co) tiles of one pixel slice share one XCD's L2
     const int nblk = gridDim.x, tiles = nblk / a.ksplit;
-    int lin;
-    {
-        const int q = nblk / 8, r = nblk % 8, xcd = blockIdx.x % 8, jj = blockIdx.x / 8;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + jj;
-    }
+    // (block decode and slab epilogue stay local in both one-tap kernels: as shared functions they changed the kernels' instructions)
+    const int lin = xcd_linear(blockIdx.x, nblk);
     const int ks = lin / tiles;
     int tile = lin - ks * tiles;
     const int ntile = tile % ntn; tile /= ntn;
@@ -161,7 +123,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_tap_bf16_kernel(const WgradArgs 
                 h[0] = (elt_t)lo[0]; h[1] = (elt_t)lo[1]; h[2] = (elt_t)lo[2]; h[3] = (elt_t)lo[3];
                 h[4] = (elt_t)hi[0]; h[5] = (elt_t)hi[1]; h[6] = (elt_t)hi[2]; h[7] = (elt_t)hi[3];
             }
-            typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
             u32x4 bits = __builtin_bit_cast(u32x4, h);
 #pragma unroll
             for (int q = 0; q < 4; ++q) bits[q] = ok ? bits[q] : 0u;       // rows outside the range / the image are zero
@@ -277,9 +238,6 @@ bool pixel_linear(const WgradArgs& a) {
 
 }  // namespace
 
-static int tile_m(const WgradArgs& a) { return a.Cin % 128 == 0 ? 128 : 64; }
-static int tile_n(const WgradArgs& a) { return a.Cout % 128 == 0 ? 128 : 64; }
-
 bool wgrad_tap_supported(const WgradArgs& a) {
     if (a.dy_s != 1 || a.dy_esz != 2 || a.nsrc != 1 || a.nseg < 1 || a.nseg > 9 || a.ashift > 1) return false;
     const SrcDev& s = a.src[0];
@@ -290,18 +248,7 @@ bool wgrad_tap_supported(const WgradArgs& a) {
     return a.Cin % 64 == 0 && a.Cout % 64 == 0;
 }
 
-// split-K plan: at most one resident round of blocks (2 per CU), at least four 64-pixel stages per block
-int wgrad_tap_plan(const WgradArgs& a, int* ksplit, long* kchunk) {
-    const long tiles = (long)(a.Cin / tile_m(a)) * (a.Cout / tile_n(a)) * a.nseg;
-    long ks = 512 / tiles;                 // rounded DOWN: 36 tiles x 15 slices = 540 blocks ran as 512 + a second round of 28
-                                           // (0.21 ms for a 0.11 ms job); 14 slices = 504 blocks finish in one round
-    if (ks > a.M / (4 * KP)) ks = a.M / (4 * KP);
-    if (ks < 1) ks = 1;
-    long chunk = (a.M + ks - 1) / ks;
-    chunk = (chunk + KP - 1) / KP * KP;
-    *kchunk = chunk; *ksplit = (int)((a.M + chunk - 1) / chunk);
-    return 0;
-}
+int wgrad_tap_plan(const WgradArgs& a, int* ksplit, long* kchunk) { return tap_plan(a, KP, ksplit, kchunk); }
 
 template <int TM, int TN, bool AFF>
 static int launch_tile_aff(const WgradArgs& a, hipStream_t st) {
@@ -320,14 +267,10 @@ static int launch_tile(const WgradArgs& a, hipStream_t st) {
     return aff ? launch_tile_aff<TM, TN, true>(a, st) : launch_tile_aff<TM, TN, false>(a, st);
 }
 
-thread_local int g_last_wgrad_variant = 0;     // (per calling thread)
-int wgrad_last_variant() { return g_last_wgrad_variant; }
-void set_last_wgrad_variant(int v) { g_last_wgrad_variant = v; }
-
 int wgrad_tap_launch_bf16(const WgradArgs& a, hipStream_t st) {
-    const int tm = tile_m(a), tn = tile_n(a);
+    const int tm = tap_tile_m(a), tn = tap_tile_n(a);
     // 'T' | TM/64 | TN/64 | loader (2 = pixel-linear 1x1, 1 = one tap, 0 = taps) | ksplit   (tests: ustrun_debug_last_wgrad_variant)
-    g_last_wgrad_variant = 0x54000000 | (tm / 64) << 20 | (tn / 64) << 16 | (pixel_linear(a) ? 2 : (a.nseg == 1 ? 1 : 0)) << 12 | (a.ksplit & 0xfff);       // (ksplit < 2^11 by the plan)
+    set_last_wgrad_variant(0x54000000 | (tm / 64) << 20 | (tn / 64) << 16 | (pixel_linear(a) ? 2 : (a.nseg == 1 ? 1 : 0)) << 12 | (a.ksplit & 0xfff));       // (ksplit < 2^11 by the plan)
     if (tm == 128 && tn == 128) return launch_tile<128, 128>(a, st);
     if (tm == 128) return launch_tile<128, 64>(a, st);
     if (tn == 128) return launch_tile<64, 128>(a, st);

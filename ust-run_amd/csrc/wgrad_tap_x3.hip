@@ -4,12 +4,10 @@
 //
 //   dW[tap][ci][co] = sum_p act(x[stride * p + dilation * (tap - k/2)][ci]) * dy[p][co]          p over the output grid
 //
-// The tiling and the WgradArgs contract are wgrad_tap_bf16.hip's: a block owns TM (128 or 64) ci x TN (128 or 64) co of one tap and a
-// contiguous range of output pixels (split-K over space), waves 2 x 2, partial slabs summed in a fixed order by reduce_partials.
-// The arithmetic is wgrad_x3_kernel's: both operands are f32 NHWC in HBM; a staged value goes global -> registers -> [BatchNorm
-// affine + ReLU in f32, zero outside the image / the pixel range] -> split4 -> three bf16 planes in LDS, [plane][pixel][channel]
-// with that kernel's row pitch and XOR of the 64-byte segments, so the K-major MFMA fragments (K = the pixel) come from the
-// transposing LDS read; a fragment pair is six MFMAs, smallest terms first, term by term over the wave's accumulators.
+// The tiling and the WgradArgs contract are wgrad_tap_bf16.hip's, the shared parts in tn_gemm.h.  The arithmetic is wgrad_x3_kernel's:
+// both operands are f32 NHWC in HBM; a staged value goes global -> registers -> [BatchNorm affine + ReLU in f32, zero outside the
+// image / the pixel range] -> split4 -> three bf16 planes in LDS, [plane][pixel][channel]; a fragment pair is six MFMAs, smallest
+// terms first, term by term over the wave's accumulators.
 //
 // Stage = 32 pixels: LDS 3 planes x 32 x (TM + TN) x 2 B = 48 KB for the 128 x 128 tile, one buffer -- the loads of stage s + 1 are
 // issued before the MFMAs of stage s and split into LDS after them; two blocks per CU (96 of 160 KB) cover each other's splits and
@@ -17,39 +15,13 @@
 // instructions of splitting per lane.
 #include "common.h"
 #include "loader.h"
+#include "tn_gemm.h"
 #include "x3_split.h"
 
 namespace ustrun {
 namespace {
 
 constexpr int KP = 32;   // pixels per stage
-
-// as wgrad_tap_bf16.hip: the 64-byte segments of a row are XOR-permuted by the row index so that the 4 rows of a transposed read
-// fall on different bank segments (256-byte rows: row & 3; 128-byte rows: (row >> 1) & 1)
-template <int RB> __device__ __forceinline__ int seg_swz(int row) { return RB >= 256 ? (row & 3) : ((row >> 1) & 1); }
-
-// rows k0 + 8*(l>>5) + {0..3 | 4..7}, columns col0 + 16*((l>>4)&1) + 4*(l&3) .. +3, delivered column-major
-template <int RB> __device__ __forceinline__ b16x8 tr_frag(const char* tile, int k0, int col0, int lane) {
-    const int q = (lane & 15) >> 2, p = lane & 3;
-    const int colb = (col0 + 16 * ((lane >> 4) & 1) + 4 * p) * 2;
-    const int r0 = k0 + 8 * (lane >> 5) + q, r1 = r0 + 4;
-    const b16x4 lo = __builtin_bit_cast(b16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((ustrun_lds_s16x4*)(tile + r0 * RB + (colb ^ (seg_swz<RB>(r0) << 6)))));
-    const b16x4 hi = __builtin_bit_cast(b16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((ustrun_lds_s16x4*)(tile + r1 * RB + (colb ^ (seg_swz<RB>(r1) << 6)))));
-    b16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-    return f;
-}
-
-// v / d and the remainder for 0 <= v < 2^24 through the float reciprocal (two fix-up steps make it exact)
-__device__ __forceinline__ int fdiv(int v, int d, float invd, int& rem) {
-    int q = (int)(((float)v + 0.5f) * invd);
-    int r = v - q * d;
-    if (r < 0) { --q; r += d; }
-    if (r >= d) { ++q; r -= d; }
-    rem = r;
-    return q;
-}
 
 // grid = (ci tiles * co tiles * taps * ksplit)
 // SWAP (1x1 convolutions): the MFMA operands trade places, D rows are co and its lanes ci, so the slab comes out as [co][ci] --
@@ -68,14 +40,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_tap_x3_kernel(const WgradArgs a,
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    // XCD-aware order (1-D grid, workgroups go round-robin over the 8 XCDs): every XCD takes a contiguous range of the
-    // (slice-major, tile-minor) order, so all (tap, ci, co) tiles of one pixel slice share one XCD's L2
     const int nblk = gridDim.x, tiles = nblk / a.ksplit;
-    int lin;
-    {
-        const int q = nblk / 8, r = nblk % 8, xcd = blockIdx.x % 8, jj = blockIdx.x / 8;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + jj;
-    }
+    // (block decode and slab epilogue stay local in both one-tap kernels: as shared functions they changed the kernels' instructions)
+    const int lin = xcd_linear(blockIdx.x, nblk);
     const int ks = lin / tiles;
     int tile = lin - ks * tiles;
     const int ntile = tile % ntn; tile /= ntn;
@@ -182,9 +149,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_tap_x3_kernel(const WgradArgs a,
 #pragma unroll
             for (int p = 0; p < 3; ++p) {
 #pragma unroll
-                for (int i = 0; i < MI; ++i) af[i][p] = tr_frag<RBA>(As + p * APLANE, kk * 16, wm * (TM / 2) + 32 * i, lane);
+                for (int i = 0; i < MI; ++i) af[i][p] = tr_frag<RBA, __bf16>(As + p * APLANE, kk * 16, wm * (TM / 2) + 32 * i, lane);
 #pragma unroll
-                for (int j = 0; j < NI; ++j) bf[j][p] = tr_frag<RBB>(Bs + p * BPLANE, kk * 16, wn * (TN / 2) + 32 * j, lane);
+                for (int j = 0; j < NI; ++j) bf[j][p] = tr_frag<RBB, __bf16>(Bs + p * BPLANE, kk * 16, wn * (TN / 2) + 32 * j, lane);
             }
             // mfma6's order (small terms first), term by term over the wave's accumulators: the six products of one accumulator
             // stand MI * NI instructions apart instead of back to back
@@ -237,9 +204,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_tap_x3_kernel(const WgradArgs a,
     }
 }
 
-int tile_m(const WgradArgs& a) { return a.Cin % 128 == 0 ? 128 : 64; }
-int tile_n(const WgradArgs& a) { return a.Cout % 128 == 0 ? 128 : 64; }
-
 template <int TM, int TN>
 int launch_tile(const WgradArgs& a, hipStream_t st) {
     const int mtn = a.Cin / TM, ntn = a.Cout / TN;
@@ -265,20 +229,10 @@ bool wgrad_tap_x3_supported(const WgradArgs& a) {
     return a.Cin % 64 == 0 && a.Cout % 64 == 0;
 }
 
-// split-K plan: at most one resident round of blocks (2 per CU), at least four 32-pixel stages per block
-int wgrad_tap_x3_plan(const WgradArgs& a, int* ksplit, long* kchunk) {
-    const long tiles = (long)(a.Cin / tile_m(a)) * (a.Cout / tile_n(a)) * a.nseg;
-    long ks = 512 / tiles;
-    if (ks > a.M / (4 * KP)) ks = a.M / (4 * KP);
-    if (ks < 1) ks = 1;
-    long chunk = (a.M + ks - 1) / ks;
-    chunk = (chunk + KP - 1) / KP * KP;
-    *kchunk = chunk; *ksplit = (int)((a.M + chunk - 1) / chunk);
-    return 0;
-}
+int wgrad_tap_x3_plan(const WgradArgs& a, int* ksplit, long* kchunk) { return tap_plan(a, KP, ksplit, kchunk); }
 
 int wgrad_tap_x3_launch(const WgradArgs& a, hipStream_t st) {
-    const int tm = tile_m(a), tn = tile_n(a);
+    const int tm = tap_tile_m(a), tn = tap_tile_n(a);
     // 'X' | TM/64 | TN/64 | slab layout (1 = one tap, [co][ci]; 0 = k x k taps, [tap][ci][co]) | ksplit   (tests: ustrun_debug_last_wgrad_variant)
     set_last_wgrad_variant(0x58000000 | (tm / 64) << 20 | (tn / 64) << 16 | (a.nseg == 1 ? 1 : 0) << 12 | (a.ksplit & 0xfff));
     if (tm == 128 && tn == 128) return launch_tile<128, 128>(a, st);

@@ -21,6 +21,7 @@
 // Everything else of this dtype (first convolution, ConvTranspose weight gradient, BatchNorm, head, losses) runs the f32 kernels.
 #include "common.h"
 #include "loader.h"
+#include "tn_gemm.h"
 #include "x3_split.h"       // split4, mfma6
 #include <type_traits>
 
@@ -464,15 +465,6 @@ constexpr int RB = 192;                                              // LDS row 
 constexpr int WAIT = TH * TW * 16 / 256;                             // float4 items per thread: activation 4,
 constexpr int WDIT = (HP * 16 + 255) / 256;                          //                          dY 7
 
-__device__ __forceinline__ b16x8 tr_frag(const char* lane_base, int k0) {
-    const b16x4 lo = __builtin_bit_cast(b16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((ustrun_lds_s16x4*)(lane_base + k0 * RB)));
-    const b16x4 hi = __builtin_bit_cast(b16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((ustrun_lds_s16x4*)(lane_base + (k0 + 4) * RB)));
-    b16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-    return f;
-}
-
 // Consumer / producer waves (as the 64 -> 64 streaming kernel of round 3): waves 0-3 read fragments and multiply, waves 4-7 fetch,
 // activate, split and write the NEXT tile into the other of two stage buffers -- one of each per SIMD, so the ~430 VALU instructions of
 // splitting a tile run under the other wave's 216 MFMAs instead of in front of them (one block of four waves per CU did both in turn:
@@ -482,15 +474,6 @@ __device__ __forceinline__ b16x8 tr_frag(const char* lane_base, int k0) {
 constexpr int RBW = 128;
 constexpr int WDROWS = (HP * 16 + 255) / 256 * 16;            // 112: every staging item of the dY patch has a row (108 .. 111: slack, never read)
 constexpr int WATILE2 = TH * TW * RBW, WDTILE2 = WDROWS * RBW, WSTAGE2 = 3 * (WATILE2 + WDTILE2);
-
-__device__ __forceinline__ b16x8 tr_fragw(const char* lane_base, int k0) {
-    const b16x4 lo = __builtin_bit_cast(b16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((ustrun_lds_s16x4*)(lane_base + k0 * RBW)));
-    const b16x4 hi = __builtin_bit_cast(b16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((ustrun_lds_s16x4*)(lane_base + (k0 + 4) * RBW)));
-    b16x8 f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-    return f;
-}
 
 // grid = (ci tiles * co tiles, ksplit); tiles_per = spatial tiles per split
 __global__ __launch_bounds__(512, 2) void wgrad_x3_kernel(const WgradArgs a, const int ntn, const int tiles_x, const int tiles_y,
@@ -632,7 +615,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3_kernel(const WgradArgs a, con
 #pragma unroll
         for (int r = 0; r < TH; ++r)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) af[r][p] = tr_fragw(cur + abase + p * WATILE2, r * TW);
+            for (int p = 0; p < 3; ++p) af[r][p] = tr_frag_rows<RBW, __bf16>(cur + abase + p * WATILE2, r * TW);
 #pragma unroll
         for (int pr = 0; pr < TH + 2; ++pr) {
 #pragma unroll
@@ -641,7 +624,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3_kernel(const WgradArgs a, con
                 const int k0 = pr * HW2 + 2 - kw;
                 b16x8 b[3];
 #pragma unroll
-                for (int p = 0; p < 3; ++p) b[p] = tr_fragw(cur + dbase4[k0 & 3] + p * WDTILE2, k0);
+                for (int p = 0; p < 3; ++p) b[p] = tr_frag_rows<RBW, __bf16>(cur + dbase4[k0 & 3] + p * WDTILE2, k0);
 #pragma unroll
                 for (int kh = 0; kh < 3; ++kh) {      // tap (kh, kw) pairs pixel row r with dY row r + 2 - kh of the patch
                     const int r = pr + kh - 2;
@@ -762,12 +745,12 @@ __global__ __launch_bounds__(256, 1) void wgradT_x3_kernel(const WgradArgs a, co
         for (int r = 0; r < UTH; ++r) {
             b16x8 af[3];
 #pragma unroll
-            for (int p = 0; p < 3; ++p) af[p] = tr_frag(Ab + p * UATILE, r * TW);
+            for (int p = 0; p < 3; ++p) af[p] = tr_frag_rows<RB, __bf16>(Ab + p * UATILE, r * TW);
 #pragma unroll
             for (int tap = 0; tap < 4; ++tap) {
                 b16x8 b[3];
 #pragma unroll
-                for (int p = 0; p < 3; ++p) b[p] = tr_frag(Db + p * UDTILE + tap * UPX * RB, r * TW);
+                for (int p = 0; p < 3; ++p) b[p] = tr_frag_rows<RB, __bf16>(Db + p * UDTILE + tap * UPX * RB, r * TW);
                 acc[tap] = mfma6(b, af, acc[tap]);      // D[co][ci]
             }
         }

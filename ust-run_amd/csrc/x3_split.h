@@ -6,11 +6,6 @@
 namespace ustrun {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 b16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 b16x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-typedef __attribute__((address_space(3))) b16x4 lds_b16x4;
 #define X3_MFMA __builtin_amdgcn_mfma_f32_32x32x16_bf16
 
 // three bf16 terms of four f32 values, each plane as two dwords (four bf16)
