@@ -1,4 +1,4 @@
-// tn_index_check.hip -- host-only check of the index helpers of ust-run_amd/csrc/tn_gemm.h over the domains their comments claim
+// tn_index_check.hip -- host-only check of the index helpers and the tile cursor of ust-run_amd/csrc/tn_gemm.h over the domains their comments claim
 // (tests/test_tn_index_host.py builds and runs it; no GPU, no device code is called).  Exit status 0 = every check passed.
 #include <cstdio>
 #include <vector>
@@ -74,6 +74,32 @@ int main() {
             if (!seen[i]) fail("xcd_linear missing", i, nblk, 0, 0, 1);
     }
     std::printf("xcd_linear: nblk = 1..4100\n");
+
+    // tile_cursor: seek(t) is image t / (ty tx), column (t mod ty tx) / ty, row t mod ty (y fastest), and k advances from seek(t0)
+    // -- one per step, or two as the two-group kernel takes them -- land on seek(t0 + k stride), up to the last tile
+    long n_cur = 0;
+    const int dims[] = {1, 2, 3, 5, 8};
+    for (int N : {1, 3})
+        for (int ty : dims)
+            for (int tx : dims) {
+                const int total = N * ty * tx;
+                for (int stride = 1; stride <= 2; ++stride)
+                    for (int t0 = 0; t0 < total; ++t0) {
+                        tile_cursor<8, 16> c;
+                        c.seek(t0, ty, tx);
+                        for (int t = t0; t < total; t += stride) {
+                            tile_cursor<8, 16> w;
+                            w.seek(t, ty, tx);
+                            const int img = t / (ty * tx), col = (t % (ty * tx)) / ty, row = t % ty;
+                            if (w.img != img || w.x0 != col * 16 || w.y0 != row * 8) fail("tile_cursor seek", t, ty, tx, w.img * 10000 + w.x0 * 10 + w.y0, img * 10000 + col * 160 + row * 8);
+                            if (c.img != w.img || c.y0 != w.y0 || c.x0 != w.x0 || c.yend != w.yend || c.xend != w.xend)
+                                fail(stride == 1 ? "tile_cursor advance x1" : "tile_cursor advance x2", t0, t, ty * 100 + tx, c.img * 10000 + c.x0 * 10 + c.y0, w.img * 10000 + w.x0 * 10 + w.y0);
+                            ++n_cur;
+                            for (int s_ = 0; s_ < stride; ++s_) c.advance();
+                        }
+                    }
+            }
+    std::printf("tile_cursor: tiles 1..8 x 1..8, N = 1 and 3, strides 1 and 2, %ld positions\n", n_cur);
 
     if (g_fail) { std::printf("%ld checks FAILED\n", g_fail); return 1; }
     std::printf("all checks passed\n");

@@ -483,6 +483,13 @@ WGRAD_CASES = [
     ("buf_cat_64_64", 4, (64, 64), 64, 24, 40, 1, 0, 0x481),
     ("buf_rows4", 5, (128,), 64, 4, 24, 1, 0, 0x481),
     ("old_512", 6, (512,), 512, 24, 40, 2, 64, 0x480),
+    # four-row tiles of the pointer-addressed build: three buffers, transfers two tiles ahead; 10 tiles in 2 slices of 5, so the
+    # two-ahead pipeline fills and drains
+    ("old_rows4", 5, (128,), 64, 4, 24, 1, 64, 0x480),
+    # its concat: the second source at an offset with a smaller extent (the zero page)
+    ("old_cat_64_64", 4, (64, 64), 64, 24, 40, 1, 64, 0x480),
+    # the pooled kernel: the source is [4, 64, 23, 42] read through its 2x2 max window (pool on load), two passes
+    ("pool_64_128", 4, (64,), 128, 11, 21, 2, 0, 0x480),
 ]
 
 
@@ -494,15 +501,19 @@ def test_wgrad_all_taps_builds_exact(case):
     g = torch.Generator().manual_seed(len(name) * 17 + n)
     ri = lambda lo, hi, *s: torch.randint(lo, hi + 1, s, generator=g).float()
     ci, gn = sum(cs), n // G
-    y0 = ri(-3, 3, n, cs[0], h, w)
+    pool = name.startswith("pool_")          # the first source is pooled on load: stored at [2 h + 1, 2 w] (an odd row is dropped)
+    sh_, sw_ = (2 * h + 1, 2 * w) if pool else (h, w)
+    y0 = ri(-3, 3, n, cs[0], sh_, sw_)
     sc = torch.tensor([0.5, 1.0, 2.0, -1.0])[torch.randint(0, 4, (G, cs[0]), generator=g)]
     sh = ri(-1, 1, G, cs[0])
     a0 = torch.relu(y0 * sc.repeat_interleave(gn, 0)[:, :, None, None] + sh.repeat_interleave(gn, 0)[:, :, None, None])
+    if pool:
+        a0 = F.max_pool2d(a0, 2)
     aff = torch.zeros(G, 4, cs[0])
     aff[:, 0], aff[:, 1] = sc, sh
     affg, y0g = aff.cuda(), nhwc16(y0)
-    srcs = [l.nhwc_src(y0g.data_ptr(), cs[0], h, w, affg.data_ptr(), affg.data_ptr() + 4 * cs[0], relu=1, gN=gn if G > 1 else 0,
-                       gstride=4 * cs[0])]
+    srcs = [l.nhwc_src(y0g.data_ptr(), cs[0], sh_, sw_, affg.data_ptr(), affg.data_ptr() + 4 * cs[0], relu=1, gN=gn if G > 1 else 0,
+                       gstride=4 * cs[0], pool=int(pool))]
     acts, keep = [a0], [affg, y0g]
     if len(cs) == 2:
         uh, uw, oy, ox = h - 3, w - 5, 2, 3

@@ -68,6 +68,45 @@ __host__ __device__ __forceinline__ int xcd_linear(unsigned bid, int nblk) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + jj;
 }
 
+// Where a block's next tile lies, for the kernels that walk a range of tiles of a batch cut into tiles_y x tiles_x tiles of TH x TW
+// pixels per image: (image, first row, first column), wave-uniform, stepped without a division.  Tiles of an image are walked
+// DOWN its columns (y fastest): the two dY halo rows a tile shares with the next one are in L2 when that tile asks for them
+// (walking along x left them a whole tile row = MBs of other blocks' traffic apart, and every halo row came from memory twice:
+// 25 % on top of dY; the halo columns now re-read instead are 12.5 %).  k advances from seek(t) give seek(t + k)
+// (tests/host/tn_index_check.hip).
+template <int TH, int TW> struct tile_cursor {
+    int img, y0, x0, yend, xend;
+    __host__ __device__ __forceinline__ void seek(int t, int tiles_y, int tiles_x) {
+        img = t / (tiles_y * tiles_x);
+        const int rem = t - img * tiles_y * tiles_x;
+        x0 = (rem / tiles_y) * TW; y0 = (rem % tiles_y) * TH;
+        yend = tiles_y * TH; xend = tiles_x * TW;
+    }
+    __host__ __device__ __forceinline__ void advance() {
+        y0 += TH;
+        if (y0 >= yend) {
+            y0 = 0; x0 += TW;
+            if (x0 >= xend) { x0 = 0; ++img; }
+        }
+    }
+};
+
+// ---- all-taps slab (wgrad_halo_bf16, the all-taps kernel of x3.hip) -------------------------------------------------------------
+// A wave's nine 32x32 accumulators D[co][ci] -> the f32 slab in the torch weight layout [Cout][Cin][3][3]: rows of D are co
+// (co_base + the MFMA's row of register r), lanes are ci, and a lane holds all nine taps of its (co, ci) pairs -> nine
+// consecutive floats.  ADD: partner holds a second set of accumulators as [tap][r][pstride floats], added on the way out.
+template <bool ADD = false>
+__device__ __forceinline__ void store_slab_oihw9(float* slab, int Cin, int ci, int co_lane, const f32x16 (&acc)[9],
+                                                 const float* partner = nullptr, int pstride = 0) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int co = co_lane + (r & 3) + 8 * (r >> 2);
+        float* o = slab + ((long)co * Cin + ci) * 9;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) o[tap] = ADD ? acc[tap][r] + partner[(tap * 16 + r) * pstride] : acc[tap][r];
+    }
+}
+
 // ---- the one-tap-per-block kernels (wgrad_tap_bf16, wgrad_tap_x3), host side ----------------------------------------------------
 // the tile of a problem, and the split-K plan for stages of KP pixels -- at most one resident round of blocks (2 per
 // CU), at least four stages per block

@@ -12,6 +12,16 @@
 // (tr_frag_rows, tn_gemm.h), nine MFMAs.  Tiles are double-buffered: one barrier per tile.  The block walks a range of
 // tiles (split-K over space) and writes one f32 slab already in the torch [Cout][Cin][3][3] layout, summed in
 // fixed order by a plain streaming reduce.
+//
+// ONE tile body, three ways to feed it.  The non-pooled builds share the 128-byte-row tiles (H3), the block placement
+// (place_block), the fragment bases (frag_bases; halo3 keeps its own copy: through the function its eight-row build
+// spilled two more registers), the 72-MFMA body (multiply_tile9), the counted wait and -- the two buffer-addressed
+// ones -- the tile loader (BufTileLoader, walking a tile_cursor of tn_gemm.h); every kernel here ends in
+// store_slab_oihw9 (tn_gemm.h).  What differs stays in the kernels:
+//   wgrad_halo_bf16_kernel        pooled sources only: the 2x2 window goes through registers (192-byte rows, its own body)
+//   wgrad_halo3_bf16_kernel<4|8>  everything by LDS-DMA, pointer-addressed: operands beyond 2 GB per image, or debug flag 64
+//   wgrad_halo4_bf16_kernel<4|8>  the same tiles, buffer-addressed: the default below 256 channels (debug flag 256 everywhere)
+//   wgrad_halo_pp_bf16_kernel     two wave groups in opposite phases over the same loader: the default from 256 channels on
 #include "common.h"
 #include "loader.h"
 #include "tn_gemm.h"
@@ -28,12 +38,19 @@ constexpr int ATILE = TH * TW * RB, DTILE = DSLOTS * 16;
 
 __device__ __attribute__((aligned(16))) const unsigned g_zero16w[4] = {0u, 0u, 0u, 0u};
 
-// grid = (ci tiles * co tiles, ksplit); tiles_per = spatial tiles per split
-template <bool POOL>
+__device__ __forceinline__ void zero_acc9(f32x16 (&acc)[9]) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+}
+
+// grid = (ci tiles * co tiles, ksplit); tiles_per = spatial tiles per split.  The source is read through its 2x2 max window
+// (pool on load: affine + ReLU on each of the four pixels, then the maximum)
 __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradArgs a, const int ntn, const int tiles_x,
                                                                  const int tiles_y, const int tiles_per) {
     constexpr int AIT = (TH * TW * 8) / 256;       // activation items (8 channels of one pixel) per thread per tile: 2
-    constexpr int NP = POOL ? 4 : 1;
+    constexpr int NP = 4;                          // pixels of the pooling window
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* As = smem;                               // 2 x activation tile [64 px][RB]
     char* Ds = smem + 2 * ATILE;                   // 2 x dY patch [108 px][RB] (+ slack to whole wave-instructions)
@@ -54,7 +71,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradArgs
     const SrcDev S = pick_src(a.src[0], a.src[1], second);
     const int cl = cg - (second ? a.src[0].C : 0);
     const bool aff = S.scale != nullptr;
-    const bool xf = aff || S.relu || POOL;
     f32x4 asc0 = {1.f, 1.f, 1.f, 1.f}, asc1 = asc0, ash0 = {0.f, 0.f, 0.f, 0.f}, ash1 = ash0;
     int cur_grp = -1;                              // batched passes: BatchNorm constants follow the tile's image
     auto load_consts = [&](int img) {
@@ -117,15 +133,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradArgs
             const int ly = y0 + (px >> 4) - S.off_y, lx = x0 + (px & 15) - S.off_x;
             if (ly >= 0 && ly < S.LH && lx >= 0 && lx < S.LW) {
                 aok |= 1u << i;
-                if (POOL) {
-                    const long p = sbase + (long)(2 * ly) * S.sH + (long)(2 * lx) * S.sW;
-                    av[i][0] = *(const bf16x8*)(sp + p);
-                    av[i][1 % NP] = *(const bf16x8*)(sp + p + S.sW);
-                    av[i][2 % NP] = *(const bf16x8*)(sp + p + S.sH);
-                    av[i][3 % NP] = *(const bf16x8*)(sp + p + S.sH + S.sW);
-                } else {
-                    av[i][0] = *(const bf16x8*)(sp + sbase + (long)ly * S.sH + (long)lx * S.sW);
-                }
+                const long p = sbase + (long)(2 * ly) * S.sH + (long)(2 * lx) * S.sW;
+                av[i][0] = *(const bf16x8*)(sp + p);
+                av[i][1] = *(const bf16x8*)(sp + p + S.sW);
+                av[i][2] = *(const bf16x8*)(sp + p + S.sH);
+                av[i][3] = *(const bf16x8*)(sp + p + S.sH + S.sW);
             }
         }
     };
@@ -138,30 +150,23 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradArgs
 #pragma unroll
             for (int q = 0; q < 8; ++q) h[q] = (elt_t)0.f;
             if ((aok >> i) & 1u) {                   // outside the source: zero (padding is applied after the activation)
-                if (xf) {
-                    f32x4 lo, hi;
-                    act8(av[i][0], lo, hi);
+                f32x4 lo, hi;
+                act8(av[i][0], lo, hi);
 #pragma unroll
-                    for (int q = 1; q < NP; ++q) {
-                        f32x4 l2, h2;
-                        act8(av[i][q], l2, h2);
-                        lo = max4(lo, l2); hi = max4(hi, h2);
-                    }
-                    h[0] = (elt_t)lo[0]; h[1] = (elt_t)lo[1]; h[2] = (elt_t)lo[2]; h[3] = (elt_t)lo[3];
-                    h[4] = (elt_t)hi[0]; h[5] = (elt_t)hi[1]; h[6] = (elt_t)hi[2]; h[7] = (elt_t)hi[3];
-                } else {
-                    h = av[i][0];
+                for (int q = 1; q < NP; ++q) {
+                    f32x4 l2, h2;
+                    act8(av[i][q], l2, h2);
+                    lo = max4(lo, l2); hi = max4(hi, h2);
                 }
+                h[0] = (elt_t)lo[0]; h[1] = (elt_t)lo[1]; h[2] = (elt_t)lo[2]; h[3] = (elt_t)lo[3];
+                h[4] = (elt_t)hi[0]; h[5] = (elt_t)hi[1]; h[6] = (elt_t)hi[2]; h[7] = (elt_t)hi[3];
             }
             *(bf16x8*)(Abuf + px * RB + c8 * 16) = h;
         }
     };
 
     f32x16 acc[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    zero_acc9(acc);
 
     // per-lane fragment bases: rows 8*(l>>5) + q, columns quadrant + 16*((l>>4)&1) + 4p
     const int lrow = 8 * (lane >> 5) + ((lane & 15) >> 2), lcol = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
@@ -204,18 +209,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradArgs
         buf ^= 1;
     }
 
-    // slab in the torch weight layout [Cout][Cin][3][3]: rows of D are co, lanes are ci, and a lane
-    // holds all nine taps of its (co, ci) pairs -> nine consecutive floats
-    float* slab = a.partials + (long)blockIdx.y * 9 * a.Cin * a.Cout;
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int ci = ci0 + wi * 32 + l31;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int co = co0 + wj * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        float* o = slab + ((long)co * a.Cin + ci) * 9;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) o[tap] = acc[tap][r];
-    }
+    store_slab_oihw9(a.partials + (long)blockIdx.y * 9 * a.Cin * a.Cout, a.Cin, ci0 + wi * 32 + (lane & 31), co0 + wj * 32 + 4 * (lane >> 5), acc);
 }
 
 // ---- non-pooled sources: everything by LDS-DMA, three tile buffers ------------------------------------------------
@@ -245,6 +239,83 @@ __device__ __forceinline__ void dma16(const void* gsrc, const char* lds_wave_bas
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(gsrc), "s"(m) : "memory", "m0");
 }
 
+// ---- what the three DMA builds below share -------------------------------------------------------------------------
+// Where a block works: its 64 x 64 (ci, co) pair and its range of tiles.  XCD order (tn_gemm.h): the (ci, co) pairs of
+// one spatial slice run on one XCD
+struct BlockPlace { int slice, ci0, co0, tbeg, tend; };
+__device__ __forceinline__ BlockPlace place_block(const WgradArgs& a, int ntn, int tiles_x, int tiles_y, int tiles_per) {
+    const int nblk = gridDim.x, pairs = nblk / a.ksplit;
+    const int lin = xcd_linear(blockIdx.x, nblk);
+    BlockPlace b;
+    b.slice = lin / pairs;
+    const int pair = lin - b.slice * pairs;
+    const int mtile = pair / ntn, ntile = pair % ntn;
+    b.ci0 = mtile * 64; b.co0 = ntile * 64;
+    const int ttotal = a.N * tiles_y * tiles_x;
+    b.tbeg = b.slice * tiles_per;
+    b.tend = min(ttotal, b.tbeg + tiles_per);
+    return b;
+}
+
+// per-lane fragment bases inside a stage {activation tile, dY patch at A3TILE}: rows 8*(l>>5) + q; the half swap of a row
+// depends on bit 1 of (k0 + row), i.e. on k0 & 3 -- activation fragments start on multiples of 16, dY fragments anywhere:
+// four bases by the start's low two bits
+__device__ __forceinline__ void frag_bases(int lane, int wi, int wj, int A3TILE, int& abase, int (&dbase4)[4]) {
+    const int lrow = 8 * (lane >> 5) + ((lane & 15) >> 2), lcolb = (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
+    abase = lrow * RB3 + ((wi * 64 + lcolb) ^ (((lrow >> 1) & 1) << 6));
+#pragma unroll
+    for (int c = 0; c < 4; ++c) dbase4[c] = A3TILE + lrow * RB3 + ((wj * 64 + lcolb) ^ ((((c + lrow) >> 1) & 1) << 6));
+}
+
+// the tile body: 72 MFMAs per four tile rows on the stage's two operands
+template <int T3>
+__device__ __forceinline__ void multiply_tile9(const char* stage, int abase, const int (&dbase4)[4], f32x16 (&acc)[9]) {
+#pragma unroll
+    for (int h = 0; h < T3 / 4; ++h) {           // four tile rows at a time: their dY fragments are patch rows 4h .. 4h+5
+        const char* Ab = stage + abase;
+        bf16x8 af[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) af[r] = tr_frag_rows<RB3>(Ab, (4 * h + r) * TW);
+        // the three dY fragments of the next patch row are in flight while this row's MFMAs run (one LDS round trip
+        // per row instead of one per fragment)
+        bf16x8 bq[2][3];
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) {
+            const int k0 = 4 * h * HW2 + 2 - kw;
+            bq[0][kw] = tr_frag_rows<RB3>(stage + dbase4[k0 & 3], k0);
+        }
+#pragma unroll
+        for (int pr = 0; pr < 6; ++pr) {
+            if (pr + 1 < 6) {
+#pragma unroll
+                for (int kw = 0; kw < 3; ++kw) {
+                    const int k0 = (4 * h + pr + 1) * HW2 + 2 - kw;
+                    bq[(pr + 1) & 1][kw] = tr_frag_rows<RB3>(stage + dbase4[k0 & 3], k0);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) {
+#pragma unroll
+                for (int kh = 0; kh < 3; ++kh) {      // tap (kh,kw) pairs tile row r with dY row r + 2 - kh of the patch
+                    const int r = pr + kh - 2;
+                    if (r >= 0 && r < 4)
+                        acc[kh * 3 + kw] = USTRUN_MFMA_32x32x16(bq[pr & 1][kw], af[r], acc[kh * 3 + kw], 0, 0, 0);   // D[co][ci]
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+
+// counted wait: everything but the newest tile's transfers has landed.  Transfers of one tile, per wave: D3IT (- 1 on the
+// waves without a last dY piece, w4 false) + A3IT
+template <int T3> __device__ __forceinline__ void wait_all_but_one_tile(bool w4) {
+    if (w4) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(H3<T3>::DIT + H3<T3>::AIT) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(H3<T3>::DIT - 1 + H3<T3>::AIT) : "memory");
+}
+
+// ---- the pointer-addressed build (described above) ------------------------------------------------------------------
 template <int T3>
 __global__ __launch_bounds__(256, 2) void wgrad_halo3_bf16_kernel(const WgradArgs a, const int ntn, const int tiles_x,
                                                                   const int tiles_y, const int tiles_per) {
@@ -255,15 +326,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo3_bf16_kernel(const WgradArg
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform: LDS-DMA bases and role tests stay scalar
     const int wi = wave >> 1, wj = wave & 1;
-    // XCD order (tn_gemm.h): the (ci, co) pairs of one spatial slice run on one XCD
-    const int nblk = gridDim.x, pairs = nblk / a.ksplit;
-    const int lin = xcd_linear(blockIdx.x, nblk);
-    const int slice = lin / pairs, pair = lin - slice * pairs;
-    const int mtile = pair / ntn, ntile = pair % ntn;
-    const int ci0 = mtile * 64, co0 = ntile * 64;
-    const int ttotal = a.N * tiles_y * tiles_x;
-    const int tbeg = slice * tiles_per;
-    const int tend = min(ttotal, tbeg + tiles_per);
+    const BlockPlace b = place_block(a, ntn, tiles_x, tiles_y, tiles_per);
+    const int slice = b.slice, ci0 = b.ci0, co0 = b.co0, tbeg = b.tbeg, tend = b.tend;
 
     // ---- activation side: item i = LDS slot tid + 256 i: pixel (tid >> 3) + 32 i, slot tid & 7; bit 1 of the pixel is a
     // thread constant, so is the channel group the slot holds ----
@@ -369,23 +433,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo3_bf16_kernel(const WgradArg
     auto tile_img = [&](int t) { return t / (tiles_y * tiles_x); };
 
     f32x16 acc[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    zero_acc9(acc);
 
-    // per-lane fragment bases: rows 8*(l>>5) + q; the half swap of a row depends on bit 1 of (k0 + row), i.e. on k0 & 3
+    // per-lane fragment bases, as frag_bases computes them (written out here: through the function the T3 = 8 build spills more)
     const int lrow = 8 * (lane >> 5) + ((lane & 15) >> 2), lcolb = (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
     int abase, dbase4[4];
     abase = lrow * RB3 + ((wi * 64 + lcolb) ^ (((lrow >> 1) & 1) << 6));
 #pragma unroll
     for (int c = 0; c < 4; ++c) dbase4[c] = A3TILE + lrow * RB3 + ((wj * 64 + lcolb) ^ ((((c + lrow) >> 1) & 1) << 6));
 
-    // transfers of one tile, per wave: D3IT (- 1 on the waves without a last dY piece) + A3IT
-    auto wait_all_but_one_tile = [&]() {
-        if (w4) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(D3IT + A3IT) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(D3IT - 1 + A3IT) : "memory");
-    };
     unsigned ok_q[3] = {0, 0, 0};                    // in-source bits of the tiles in flight (tile t + k at index k)
     char* st[3] = {smem, smem + STAGE3, smem + (NBUF - 1) * STAGE3};     // buffers of tile t, t+1, (t+2)
     constexpr int PD = NBUF - 1;                     // tiles issued ahead
@@ -394,7 +450,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo3_bf16_kernel(const WgradArg
         ok_q[0] = issue_tile(tbeg, st[0]);
         if (PD == 2 && tbeg + 1 < tend) {
             ok_q[1] = issue_tile(tbeg + 1, st[1]);
-            wait_all_but_one_tile();
+            wait_all_but_one_tile<T3>(w4);
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -406,46 +462,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo3_bf16_kernel(const WgradArg
         // top: tile t+PD into the buffer tile t-1 used
         const bool issue = t + PD < tend;
         if (issue) ok_q[PD] = issue_tile(t + PD, st[PD]);
-#pragma unroll
-        for (int h = 0; h < T3 / 4; ++h) {           // four tile rows at a time: their dY fragments are patch rows 4h .. 4h+5
-            const char* Ab = st[0] + abase;
-            bf16x8 af[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) af[r] = tr_frag_rows<RB3>(Ab, (4 * h + r) * TW);
-            // the three dY fragments of the next patch row are in flight while this row's MFMAs run (one LDS round trip
-            // per row instead of one per fragment)
-            bf16x8 bq[2][3];
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int k0 = 4 * h * HW2 + 2 - kw;
-                bq[0][kw] = tr_frag_rows<RB3>(st[0] + dbase4[k0 & 3], k0);
-            }
-#pragma unroll
-            for (int pr = 0; pr < 6; ++pr) {
-                if (pr + 1 < 6) {
-#pragma unroll
-                    for (int kw = 0; kw < 3; ++kw) {
-                        const int k0 = (4 * h + pr + 1) * HW2 + 2 - kw;
-                        bq[(pr + 1) & 1][kw] = tr_frag_rows<RB3>(st[0] + dbase4[k0 & 3], k0);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int kw = 0; kw < 3; ++kw) {
-#pragma unroll
-                    for (int kh = 0; kh < 3; ++kh) {      // tap (kh,kw) pairs tile row r with dY row r + 2 - kh of the patch
-                        const int r = pr + kh - 2;
-                        if (r >= 0 && r < 4)
-                            acc[kh * 3 + kw] = USTRUN_MFMA_32x32x16(bq[pr & 1][kw], af[r], acc[kh * 3 + kw], 0, 0, 0);   // D[co][ci]
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
+        multiply_tile9<T3>(st[0], abase, dbase4, acc);
         // bottom: tile t+1 has landed once only the transfers of later tiles are outstanding
         __builtin_amdgcn_sched_barrier(0);          // keep the waits behind the MFMAs
         if (t + 1 < tend) {
-            if (PD == 2 && issue) wait_all_but_one_tile();
+            if (PD == 2 && issue) wait_all_but_one_tile<T3>(w4);
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             load_consts(tile_img(t + 1));
             activate(st[1], ok_q[1]);
@@ -457,16 +478,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo3_bf16_kernel(const WgradArg
         else { char* tmp = st[0]; st[0] = st[1]; st[1] = tmp; st[2] = st[1]; ok_q[0] = ok_q[1]; }
     }
 
-    float* slab = a.partials + (long)slice * 9 * a.Cin * a.Cout;
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int ci = ci0 + wi * 32 + l31;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int co = co0 + wj * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        float* o = slab + ((long)co * a.Cin + ci) * 9;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) o[tap] = acc[tap][r];
-    }
+    store_slab_oihw9(a.partials + (long)slice * 9 * a.Cin * a.Cout, a.Cin, ci0 + wi * 32 + (lane & 31), co0 + wj * 32 + 4 * (lane >> 5), acc);
 }
 
 
@@ -483,81 +495,75 @@ __device__ __forceinline__ void dma16_buf(int voff, __amdgpu_buffer_rsrc_t rs, c
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" :: "v"(voff), "s"(rs), "s"(m) : "memory", "m0");
 }
 
-template <int T3>
-__global__ __launch_bounds__(256, 2) void wgrad_halo4_bf16_kernel(const WgradArgs a, const int ntn, const int tiles_x,
-                                                                  const int tiles_y, const int tiles_per) {
+// The tile loader of the two buffer-addressed kernels: the per-lane constants, the cursor of the next tile to issue and the
+// three things done with a stage buffer.  gt = the thread's index within its 256-thread group, STEP = tiles the cursor
+// moves per issued tile (1; 2 where two groups share a block's range), NACT = activation items per LDS round trip.
+template <int T3, int STEP, int NACT>
+struct BufTileLoader {
     typedef H3<T3> G;
-    constexpr int A3IT = G::AIT, D3IT = G::DIT, D3SLOTS = G::DSLOTS, A3TILE = G::ATILE, STAGE3 = G::STAGE, NBUF = G::NBUF;
-    constexpr int HPX = G::HPX;
-    constexpr int OOB = (int)0x80000000;
-    extern __shared__ __attribute__((aligned(16))) char smem[];   // NBUF x {activation tile [T3*16 px][128 B], dY patch [HPX px][128 B]}
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wi = wave >> 1, wj = wave & 1;
-    const int nblk = gridDim.x, pairs = nblk / a.ksplit;
-    const int lin = xcd_linear(blockIdx.x, nblk);
-    const int slice = lin / pairs, pair = lin - slice * pairs;
-    const int mtile = pair / ntn, ntile = pair % ntn;
-    const int ci0 = mtile * 64, co0 = ntile * 64;
-    const int ttotal = a.N * tiles_y * tiles_x;
-    const int tbeg = slice * tiles_per;
-    const int tend = min(ttotal, tbeg + tiles_per);
+    static constexpr int A3IT = G::AIT, D3IT = G::DIT, A3TILE = G::ATILE;
+    static constexpr int OOB = (int)0x80000000;
+    const WgradArgs& a;
+    const int gt, wave;
+    SrcDev S;
+    bool xf, w4;
+    int cl0, apx, agl;
+    f32x4 asc0, asc1, ash0, ash1;
+    int cur_grp;
+    int sH2, sW2, aoff[A3IT], droff[D3IT], dhyx[D3IT];
+    const char* sbytes;
+    const char* dbytes;
+    long sN2, dN2;
+    int dW2, dP2;
+    tile_cursor<T3, TW> q;                         // the next tile to issue (wave-uniform)
 
-    // the 64 input channels of a block come from ONE source (source widths are multiples of 64)
-    const bool second = (a.nsrc == 2 && ci0 >= a.src[0].C);
-    const SrcDev S = pick_src(a.src[0], a.src[1], second);
-    const int cl0 = ci0 - (second ? a.src[0].C : 0);
-    const bool aff = S.scale != nullptr;
-    const bool xf = aff || S.relu;
-    const int apx = tid >> 3;
-    const int agl = (tid & 7) ^ (((apx >> 1) & 1) << 2);
-    f32x4 asc0 = {1.f, 1.f, 1.f, 1.f}, asc1 = asc0, ash0 = {0.f, 0.f, 0.f, 0.f}, ash1 = ash0;
-    int cur_grp = -1;
-    auto load_consts = [&](int img) {
+    __device__ __forceinline__ BufTileLoader(const WgradArgs& a_, int ci0, int co0, int gt_, int wave_, int t0, int tiles_y, int tiles_x)
+        : a(a_), gt(gt_), wave(wave_) {
+        // the 64 input channels of a block come from ONE source (source widths are multiples of 64)
+        const bool second = (a.nsrc == 2 && ci0 >= a.src[0].C);
+        S = pick_src(a.src[0], a.src[1], second);
+        cl0 = ci0 - (second ? a.src[0].C : 0);
+        xf = S.scale != nullptr || S.relu;
+        apx = gt >> 3;
+        agl = (gt & 7) ^ (((apx >> 1) & 1) << 2);
+        asc0 = (f32x4){1.f, 1.f, 1.f, 1.f}; asc1 = asc0; ash0 = (f32x4){0.f, 0.f, 0.f, 0.f}; ash1 = ash0;
+        cur_grp = -1;
+        const int dyW = a.dyW, Cout = a.Cout;       // read once, ahead of the per-item selects: the strides below must stay wave-uniform
+        // tile-invariant per-lane byte offsets from the tile's base: activation item i = pixel apx + 32 i (row 2 i + (apx >> 4),
+        // column apx & 15), channel group agl; dY item i = slot gt + 256 i of the patch
+        sH2 = (int)S.sH * 2; sW2 = (int)S.sW * 2;
+#pragma unroll
+        for (int i = 0; i < A3IT; ++i) aoff[i] = (2 * i + (apx >> 4)) * sH2 + (apx & 15) * sW2 + (cl0 + 8 * agl) * 2;
+#pragma unroll
+        for (int i = 0; i < D3IT; ++i) {
+            const int slot = gt + 256 * i, hp = slot >> 3;
+            const int gl = (slot & 7) ^ (((hp >> 1) & 1) << 2);
+            const int hy = hp / HW2, hx = hp - hy * HW2;
+            const bool v = hp < G::HPX;
+            droff[i] = v ? ((hy * dyW + hx) * Cout + 8 * gl) * 2 : OOB;
+            dhyx[i] = v ? ((hy << 8) | hx) : 0xffff;
+        }
+        w4 = 256 * (D3IT - 1) + wave * 64 < G::DSLOTS;       // does this wave issue the last dY piece?
+        sbytes = (const char*)S.ptr;
+        dbytes = (const char*)a.dy + 2 * co0;
+        sN2 = S.sN * 2; dN2 = (long)a.dyH * dyW * Cout * 2;
+        dW2 = dyW * Cout * 2; dP2 = Cout * 2;
+        q.seek(t0, tiles_y, tiles_x);
+    }
+    // batched passes: BatchNorm constants follow the tile's image
+    __device__ __forceinline__ void load_consts(int img) {
         const int grp = S.gN > 0 ? img / S.gN : 0;
-        if (aff && grp != cur_grp) {
+        if (S.scale != nullptr && grp != cur_grp) {
             const long o = (long)grp * (S.gN > 0 ? S.gstride : 0) + cl0 + 8 * agl;
             asc0 = *(const f32x4*)(S.scale + o); asc1 = *(const f32x4*)(S.scale + o + 4);
             ash0 = *(const f32x4*)(S.shift + o); ash1 = *(const f32x4*)(S.shift + o + 4);
             cur_grp = grp;
         }
-    };
-    // tile-invariant per-lane byte offsets from the tile's base: activation item i = pixel apx + 32 i (row 2 i + (apx >> 4),
-    // column apx & 15), channel group agl; dY item i = slot tid + 256 i of the patch
-    const int sH2 = (int)S.sH * 2, sW2 = (int)S.sW * 2;
-    int aoff[A3IT];
-#pragma unroll
-    for (int i = 0; i < A3IT; ++i) aoff[i] = (2 * i + (apx >> 4)) * sH2 + (apx & 15) * sW2 + (cl0 + 8 * agl) * 2;
-    int droff[D3IT], dhyx[D3IT];
-#pragma unroll
-    for (int i = 0; i < D3IT; ++i) {
-        const int slot = tid + 256 * i, hp = slot >> 3;
-        const int gl = (slot & 7) ^ (((hp >> 1) & 1) << 2);
-        const int hy = hp / HW2, hx = hp - hy * HW2;
-        const bool v = hp < HPX;
-        droff[i] = v ? ((hy * a.dyW + hx) * a.Cout + 8 * gl) * 2 : OOB;
-        dhyx[i] = v ? ((hy << 8) | hx) : 0xffff;
-    }
-    const bool w4 = 256 * (D3IT - 1) + wave * 64 < D3SLOTS;       // does this wave issue the last dY piece?
-    const char* const sbytes = (const char*)S.ptr;
-    const char* const dbytes = (const char*)a.dy + 2 * co0;
-    const long sN2 = S.sN * 2, dN2 = (long)a.dyH * a.dyW * a.Cout * 2;
-    const int dW2 = a.dyW * a.Cout * 2, dP2 = a.Cout * 2;
-
-    // cursor of the next tile to issue (wave-uniform)
-    // tiles of an image are walked DOWN its columns (y fastest): the two dY halo rows a tile shares with the next one are in L2
-    // when that tile asks for them (walking along x left them a whole tile row = MBs of other blocks' traffic apart, and every
-    // halo row came from memory twice: 25 % on top of dY; the halo columns now re-read instead are 12.5 %)
-    int q_img, q_y0, q_x0;
-    {
-        q_img = tbeg / (tiles_y * tiles_x);
-        const int rem = tbeg - q_img * tiles_y * tiles_x;
-        q_x0 = (rem / tiles_y) * TW; q_y0 = (rem % tiles_y) * T3;
     }
     // all transfers of the cursor's tile -> stage buffer; bit i of the result: activation item i lies in the source; bit 8: the
     // whole activation tile does (no masks needed); bits 16..: the tile's image
-    auto issue_tile = [&](char* stage) {
-        const int img = q_img, y0 = q_y0, x0 = q_x0;
+    __device__ __forceinline__ unsigned issue_tile(char* stage) {
+        const int img = q.img, y0 = q.y0, x0 = q.x0;
         {
             const char* dbase = dbytes + (long)img * dN2 + ((y0 - 1) * dW2 + (x0 - 1) * dP2);
             const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)dbase, 0, 0x7fffffff, 0x00020000);
@@ -599,21 +605,18 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo4_bf16_kernel(const WgradArg
             }
         }
         ok2 |= (unsigned)img << 16;
-        q_y0 += T3;
-        if (q_y0 >= tiles_y * T3) {
-            q_y0 = 0; q_x0 += TW;
-            if (q_x0 >= tiles_x * TW) { q_x0 = 0; ++q_img; }
-        }
+#pragma unroll
+        for (int s = 0; s < STEP; ++s) q.advance();
         return ok2;
-    };
-    // BatchNorm affine + ReLU of this thread's items, in place (items outside the source stay zero)
-    auto act_item = [&](u32x4 r, bool relu) {
+    }
+    // BatchNorm affine + ReLU of one item
+    __device__ __forceinline__ u32x4 act_item(u32x4 r, bool relu) const {
         const bf16x8 b = __builtin_bit_cast(bf16x8, r);
         f32x4 lo, hi;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {              // scalar FMAs on purpose: beside another wave's MFMAs a v_pk_fma_f32 costs more than two v_fma_f32
-            lo[q] = fma_scalar((float)b[q], asc0[q], ash0[q]);
-            hi[q] = fma_scalar((float)b[4 + q], asc1[q], ash1[q]);
+        for (int q_ = 0; q_ < 4; ++q_) {           // scalar FMAs on purpose: beside another wave's MFMAs a v_pk_fma_f32 costs more than two v_fma_f32
+            lo[q_] = fma_scalar((float)b[q_], asc0[q_], ash0[q_]);
+            hi[q_] = fma_scalar((float)b[4 + q_], asc1[q_], ash1[q_]);
         }
         bf16x8 h;
         h[0] = (elt_t)lo[0]; h[1] = (elt_t)lo[1]; h[2] = (elt_t)lo[2]; h[3] = (elt_t)lo[3];
@@ -623,103 +626,75 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo4_bf16_kernel(const WgradArg
             return __builtin_bit_cast(u32x4, __builtin_elementwise_max(__builtin_bit_cast(s16x8, h), z));
         }
         return __builtin_bit_cast(u32x4, h);
-    };
-    auto activate = [&](char* stage, unsigned ok2) {
+    }
+    // BatchNorm affine + ReLU of this thread's items, in place (items outside the source stay zero), NACT items per LDS
+    // round trip
+    __device__ __forceinline__ void activate(char* stage, unsigned ok2) const {
         if (!xf) return;
         const bool inner = (ok2 >> 8) & 1u;
 #pragma unroll
-        for (int i0 = 0; i0 < A3IT; i0 += 2) {              // two items per LDS round trip (four would spill)
-            u32x4 r[2];
+        for (int i0 = 0; i0 < A3IT; i0 += NACT) {
+            u32x4 r[NACT];
 #pragma unroll
-            for (int i = 0; i < 2; ++i) r[i] = *(const u32x4*)(stage + (tid + 256 * (i0 + i)) * 16);
+            for (int i = 0; i < NACT; ++i) r[i] = *(const u32x4*)(stage + (gt + 256 * (i0 + i)) * 16);
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
+            for (int i = 0; i < NACT; ++i) {
                 u32x4 u = S.relu ? act_item(r[i], true) : act_item(r[i], false);
                 if (!inner) {
                     const bool ok = (ok2 >> (i0 + i)) & 1u;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) u[q] = ok ? u[q] : 0u;
+                    for (int q_ = 0; q_ < 4; ++q_) u[q_] = ok ? u[q_] : 0u;
                 }
-                *(u32x4*)(stage + (tid + 256 * (i0 + i)) * 16) = u;
+                *(u32x4*)(stage + (gt + 256 * (i0 + i)) * 16) = u;
             }
         }
-    };
+    }
+};
+
+template <int T3>
+__global__ __launch_bounds__(256, 2) void wgrad_halo4_bf16_kernel(const WgradArgs a, const int ntn, const int tiles_x,
+                                                                  const int tiles_y, const int tiles_per) {
+    typedef H3<T3> G;
+    constexpr int STAGE3 = G::STAGE, NBUF = G::NBUF;
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // NBUF x {activation tile [T3*16 px][128 B], dY patch [HPX px][128 B]}
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wi = wave >> 1, wj = wave & 1;
+    const BlockPlace b = place_block(a, ntn, tiles_x, tiles_y, tiles_per);
+    const int tbeg = b.tbeg, tend = b.tend;
+    BufTileLoader<T3, 1, 2> ld(a, b.ci0, b.co0, tid, wave, tbeg, tiles_y, tiles_x);      // two items per LDS round trip (four would spill)
 
     f32x16 acc[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-    const int lrow = 8 * (lane >> 5) + ((lane & 15) >> 2), lcolb = (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
+    zero_acc9(acc);
     int abase, dbase4[4];
-    abase = lrow * RB3 + ((wi * 64 + lcolb) ^ (((lrow >> 1) & 1) << 6));
-#pragma unroll
-    for (int c = 0; c < 4; ++c) dbase4[c] = A3TILE + lrow * RB3 + ((wj * 64 + lcolb) ^ ((((c + lrow) >> 1) & 1) << 6));
+    frag_bases(lane, wi, wj, G::ATILE, abase, dbase4);
 
-    auto wait_all_but_one_tile = [&]() {
-        if (w4) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(D3IT + A3IT) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(D3IT - 1 + A3IT) : "memory");
-    };
     unsigned ok_q[3] = {0, 0, 0};
     char* st[3] = {smem, smem + STAGE3, smem + (NBUF - 1) * STAGE3};
     constexpr int PD = NBUF - 1;
     if (tbeg < tend) {
-        ok_q[0] = issue_tile(st[0]);
-        load_consts(ok_q[0] >> 16);
+        ok_q[0] = ld.issue_tile(st[0]);
+        ld.load_consts(ok_q[0] >> 16);
         if (PD == 2 && tbeg + 1 < tend) {
-            ok_q[1] = issue_tile(st[1]);
-            wait_all_but_one_tile();
+            ok_q[1] = ld.issue_tile(st[1]);
+            wait_all_but_one_tile<T3>(ld.w4);
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        activate(st[0], ok_q[0]);
+        ld.activate(st[0], ok_q[0]);
     }
     __syncthreads();
 #pragma unroll 1
     for (int t = tbeg; t < tend; ++t) {
         const bool issue = t + PD < tend;
-        if (issue) ok_q[PD] = issue_tile(st[PD]);
-#pragma unroll
-        for (int h = 0; h < T3 / 4; ++h) {
-            const char* Ab = st[0] + abase;
-            bf16x8 af[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) af[r] = tr_frag_rows<RB3>(Ab, (4 * h + r) * TW);
-            bf16x8 bq[2][3];
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int k0 = 4 * h * HW2 + 2 - kw;
-                bq[0][kw] = tr_frag_rows<RB3>(st[0] + dbase4[k0 & 3], k0);
-            }
-#pragma unroll
-            for (int pr = 0; pr < 6; ++pr) {
-                if (pr + 1 < 6) {
-#pragma unroll
-                    for (int kw = 0; kw < 3; ++kw) {
-                        const int k0 = (4 * h + pr + 1) * HW2 + 2 - kw;
-                        bq[(pr + 1) & 1][kw] = tr_frag_rows<RB3>(st[0] + dbase4[k0 & 3], k0);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int kw = 0; kw < 3; ++kw) {
-#pragma unroll
-                    for (int kh = 0; kh < 3; ++kh) {
-                        const int r = pr + kh - 2;
-                        if (r >= 0 && r < 4)
-                            acc[kh * 3 + kw] = USTRUN_MFMA_32x32x16(bq[pr & 1][kw], af[r], acc[kh * 3 + kw], 0, 0, 0);   // D[co][ci]
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
+        if (issue) ok_q[PD] = ld.issue_tile(st[PD]);
+        multiply_tile9<T3>(st[0], abase, dbase4, acc);
         __builtin_amdgcn_sched_barrier(0);
         if (t + 1 < tend) {
-            if (PD == 2 && issue) wait_all_but_one_tile();
+            if (PD == 2 && issue) wait_all_but_one_tile<T3>(ld.w4);
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            load_consts(ok_q[1] >> 16);
-            activate(st[1], ok_q[1]);
+            ld.load_consts(ok_q[1] >> 16);
+            ld.activate(st[1], ok_q[1]);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -728,18 +703,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo4_bf16_kernel(const WgradArg
         else { char* tmp = st[0]; st[0] = st[1]; st[1] = tmp; st[2] = st[1]; ok_q[0] = ok_q[1]; }
     }
 
-    float* slab = a.partials + (long)slice * 9 * a.Cin * a.Cout;
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int ci = ci0 + wi * 32 + l31;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int co = co0 + wj * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        float* o = slab + ((long)co * a.Cin + ci) * 9;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) o[tap] = acc[tap][r];
-    }
+    store_slab_oihw9(a.partials + (long)b.slice * 9 * a.Cin * a.Cout, a.Cin, b.ci0 + wi * 32 + (lane & 31), b.co0 + wj * 32 + 4 * (lane >> 5), acc);
 }
-
 
 // ---- round 3: two wave groups in opposite phases ("ping-pong") ------------------------------------------------------
 // Two 256-thread blocks per CU run the kernel above in step with each other: both multiply at the same time (sharing
@@ -767,216 +732,29 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_pp_bf16_kernel(const WgradA
                                                                     unsigned long long* __restrict__ dbg) {
     constexpr int T3 = 8;
     typedef H3<T3> G;
-    constexpr int A3IT = G::AIT, D3IT = G::DIT, D3SLOTS = G::DSLOTS, A3TILE = G::ATILE, STAGE3 = G::STAGE;
-    constexpr int HPX = G::HPX;
-    constexpr int OOB = (int)0x80000000;
+    constexpr int STAGE3 = G::STAGE;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 groups x 2 x {activation tile, dY patch}
     const int lane = threadIdx.x & 63, gt = threadIdx.x & 255;
     const int wave8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = wave8 >> 2, wave = wave8 & 3;
     const int wi = wave >> 1, wj = wave & 1;
-    const int nblk = gridDim.x, pairs = nblk / a.ksplit;
-    const int lin = xcd_linear(blockIdx.x, nblk);
-    const int slice = lin / pairs, pair = lin - slice * pairs;
-    const int mtile = pair / ntn, ntile = pair % ntn;
-    const int ci0 = mtile * 64, co0 = ntile * 64;
-    const int ttotal = a.N * tiles_y * tiles_x;
-    const int tbeg = slice * tiles_per;
-    const int tend = min(ttotal, tbeg + tiles_per);
-    const int ntl = max(tend - tbeg, 0);
+    const BlockPlace b = place_block(a, ntn, tiles_x, tiles_y, tiles_per);
+    const int ntl = max(b.tend - b.tbeg, 0);
     const int nk = (ntl + 1 - grp) >> 1;                            // this group's tiles: tbeg + grp + 2 k
     const int pend = max(2 * (((ntl + 1) >> 1) - 1), 2 * ((ntl >> 1) - 1) + 1);     // last phase with a multiplication
 
-    const bool second = (a.nsrc == 2 && ci0 >= a.src[0].C);
-    const SrcDev S = pick_src(a.src[0], a.src[1], second);
-    const int cl0 = ci0 - (second ? a.src[0].C : 0);
-    const bool aff = S.scale != nullptr;
-    const bool xf = aff || S.relu;
-    const int apx = gt >> 3;
-    const int agl = (gt & 7) ^ (((apx >> 1) & 1) << 2);
-    f32x4 asc0 = {1.f, 1.f, 1.f, 1.f}, asc1 = asc0, ash0 = {0.f, 0.f, 0.f, 0.f}, ash1 = ash0;
-    int cur_grp = -1;
-    auto load_consts = [&](int img) {
-        const int g = S.gN > 0 ? img / S.gN : 0;
-        if (aff && g != cur_grp) {
-            const long o = (long)g * (S.gN > 0 ? S.gstride : 0) + cl0 + 8 * agl;
-            asc0 = *(const f32x4*)(S.scale + o); asc1 = *(const f32x4*)(S.scale + o + 4);
-            ash0 = *(const f32x4*)(S.shift + o); ash1 = *(const f32x4*)(S.shift + o + 4);
-            cur_grp = g;
-        }
-    };
-    const int sH2 = (int)S.sH * 2, sW2 = (int)S.sW * 2;
-    int aoff[A3IT];
-#pragma unroll
-    for (int i = 0; i < A3IT; ++i) aoff[i] = (2 * i + (apx >> 4)) * sH2 + (apx & 15) * sW2 + (cl0 + 8 * agl) * 2;
-    int droff[D3IT], dhyx[D3IT];
-#pragma unroll
-    for (int i = 0; i < D3IT; ++i) {
-        const int slot = gt + 256 * i, hp = slot >> 3;
-        const int gl = (slot & 7) ^ (((hp >> 1) & 1) << 2);
-        const int hy = hp / HW2, hx = hp - hy * HW2;
-        const bool v = hp < HPX;
-        droff[i] = v ? ((hy * a.dyW + hx) * a.Cout + 8 * gl) * 2 : OOB;
-        dhyx[i] = v ? ((hy << 8) | hx) : 0xffff;
-    }
-    const bool w4 = 256 * (D3IT - 1) + wave * 64 < D3SLOTS;
-    const char* const sbytes = (const char*)S.ptr;
-    const char* const dbytes = (const char*)a.dy + 2 * co0;
-    const long sN2 = S.sN * 2, dN2 = (long)a.dyH * a.dyW * a.Cout * 2;
-    const int dW2 = a.dyW * a.Cout * 2, dP2 = a.Cout * 2;
-
-    int q_img, q_y0, q_x0;                                          // cursor of the group's next tile to issue
-    {
-        const int t0 = tbeg + grp;                                  // (y fastest, as in the kernel above)
-        q_img = t0 / (tiles_y * tiles_x);
-        const int rem = t0 - q_img * tiles_y * tiles_x;
-        q_x0 = (rem / tiles_y) * TW; q_y0 = (rem % tiles_y) * T3;
-    }
-    auto issue_tile = [&](char* stage) {
-        const int img = q_img, y0 = q_y0, x0 = q_x0;
-        {
-            const char* dbase = dbytes + (long)img * dN2 + ((y0 - 1) * dW2 + (x0 - 1) * dP2);
-            const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)dbase, 0, 0x7fffffff, 0x00020000);
-            const bool inner = y0 >= 1 && y0 + T3 + 1 <= a.dyH && x0 >= 1 && x0 + TW + 1 <= a.dyW;
-            if (inner) {
-#pragma unroll
-                for (int i = 0; i < D3IT; ++i)
-                    if (i < D3IT - 1 || w4) dma16_buf(droff[i], rd, stage + A3TILE + (256 * i + wave * 64) * 16);
-            } else {
-#pragma unroll
-                for (int i = 0; i < D3IT; ++i) {
-                    if (i < D3IT - 1 || w4) {
-                        const unsigned ly = (unsigned)(y0 - 1 + (dhyx[i] >> 8)), lx = (unsigned)(x0 - 1 + (dhyx[i] & 0xff));
-                        const bool ok = ly < (unsigned)a.dyH && lx < (unsigned)a.dyW;
-                        dma16_buf(ok ? droff[i] : OOB, rd, stage + A3TILE + (256 * i + wave * 64) * 16);
-                    }
-                }
-            }
-        }
-        unsigned ok2;
-        {
-            const int ty = y0 - S.off_y, tx = x0 - S.off_x;
-            const char* abase = sbytes + (long)img * sN2 + (ty * sH2 + tx * sW2);
-            const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)abase, 0, 0x7fffffff, 0x00020000);
-            const bool inner = ty >= 0 && ty + T3 <= S.LH && tx >= 0 && tx + TW <= S.LW;
-            if (inner) {
-                ok2 = 0x100u | ((1u << A3IT) - 1u);
-#pragma unroll
-                for (int i = 0; i < A3IT; ++i) dma16_buf(aoff[i], ra, stage + (256 * i + wave * 64) * 16);
-            } else {
-                ok2 = 0;
-#pragma unroll
-                for (int i = 0; i < A3IT; ++i) {
-                    const unsigned ly = (unsigned)(ty + 2 * i + (apx >> 4)), lx = (unsigned)(tx + (apx & 15));
-                    const bool ok = ly < (unsigned)S.LH && lx < (unsigned)S.LW;
-                    ok2 |= (ok ? 1u : 0u) << i;
-                    dma16_buf(ok ? aoff[i] : OOB, ra, stage + (256 * i + wave * 64) * 16);
-                }
-            }
-        }
-        ok2 |= (unsigned)img << 16;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {                               // the group's next tile is two tiles on
-            q_y0 += T3;
-            if (q_y0 >= tiles_y * T3) {
-                q_y0 = 0; q_x0 += TW;
-                if (q_x0 >= tiles_x * TW) { q_x0 = 0; ++q_img; }
-            }
-        }
-        return ok2;
-    };
-    auto act_item = [&](u32x4 r, bool relu) {
-        const bf16x8 b = __builtin_bit_cast(bf16x8, r);
-        f32x4 lo, hi;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {              // scalar FMAs on purpose: beside another wave's MFMAs a v_pk_fma_f32 costs more than two v_fma_f32
-            lo[q] = fma_scalar((float)b[q], asc0[q], ash0[q]);
-            hi[q] = fma_scalar((float)b[4 + q], asc1[q], ash1[q]);
-        }
-        bf16x8 h;
-        h[0] = (elt_t)lo[0]; h[1] = (elt_t)lo[1]; h[2] = (elt_t)lo[2]; h[3] = (elt_t)lo[3];
-        h[4] = (elt_t)hi[0]; h[5] = (elt_t)hi[1]; h[6] = (elt_t)hi[2]; h[7] = (elt_t)hi[3];
-        if (relu) {
-            const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-            return __builtin_bit_cast(u32x4, __builtin_elementwise_max(__builtin_bit_cast(s16x8, h), z));
-        }
-        return __builtin_bit_cast(u32x4, h);
-    };
-    auto activate = [&](char* stage, unsigned ok2) {
-        if (!xf) return;
-        const bool inner = (ok2 >> 8) & 1u;
-        u32x4 r[A3IT];
-#pragma unroll
-        for (int i = 0; i < A3IT; ++i) r[i] = *(const u32x4*)(stage + (gt + 256 * i) * 16);       // one LDS round trip
-#pragma unroll
-        for (int i = 0; i < A3IT; ++i) {
-            u32x4 u = S.relu ? act_item(r[i], true) : act_item(r[i], false);
-            if (!inner) {
-                const bool ok = (ok2 >> i) & 1u;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) u[q] = ok ? u[q] : 0u;
-            }
-            *(u32x4*)(stage + (gt + 256 * i) * 16) = u;
-        }
-    };
+    // the group's cursor starts at its first tile and moves two tiles per issue; all items of a tile in one LDS round trip
+    BufTileLoader<T3, 2, G::AIT> ld(a, b.ci0, b.co0, gt, wave, b.tbeg + grp, tiles_y, tiles_x);
 
     f32x16 acc[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-    const int lrow = 8 * (lane >> 5) + ((lane & 15) >> 2), lcolb = (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
+    zero_acc9(acc);
     int abase, dbase4[4];
-    abase = lrow * RB3 + ((wi * 64 + lcolb) ^ (((lrow >> 1) & 1) << 6));
-#pragma unroll
-    for (int c = 0; c < 4; ++c) dbase4[c] = A3TILE + lrow * RB3 + ((wj * 64 + lcolb) ^ ((((c + lrow) >> 1) & 1) << 6));
-
-    auto multiply_tile = [&](const char* stage) {
-#pragma unroll
-        for (int h = 0; h < T3 / 4; ++h) {
-            const char* Ab = stage + abase;
-            bf16x8 af[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) af[r] = tr_frag_rows<RB3>(Ab, (4 * h + r) * TW);
-            bf16x8 bq[2][3];
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int k0 = 4 * h * HW2 + 2 - kw;
-                bq[0][kw] = tr_frag_rows<RB3>(stage + dbase4[k0 & 3], k0);
-            }
-#pragma unroll
-            for (int pr = 0; pr < 6; ++pr) {
-                if (pr + 1 < 6) {
-#pragma unroll
-                    for (int kw = 0; kw < 3; ++kw) {
-                        const int k0 = (4 * h + pr + 1) * HW2 + 2 - kw;
-                        bq[(pr + 1) & 1][kw] = tr_frag_rows<RB3>(stage + dbase4[k0 & 3], k0);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int kw = 0; kw < 3; ++kw) {
-#pragma unroll
-                    for (int kh = 0; kh < 3; ++kh) {
-                        const int r = pr + kh - 2;
-                        if (r >= 0 && r < 4)
-                            acc[kh * 3 + kw] = USTRUN_MFMA_32x32x16(bq[pr & 1][kw], af[r], acc[kh * 3 + kw], 0, 0, 0);   // D[co][ci]
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    };
-    auto wait_all_but_one_tile = [&]() {
-        if (w4) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(D3IT + A3IT) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(D3IT - 1 + A3IT) : "memory");
-    };
+    frag_bases(lane, wi, wj, G::ATILE, abase, dbase4);
 
     char* stC = smem + grp * 2 * STAGE3;           // the group's current tile (being activated, then multiplied)
     char* stN = stC + STAGE3;                      // the tile after it (in flight)
     unsigned okC = 0, okN = 0;
-    if (nk > 0) okC = issue_tile(stC);
+    if (nk > 0) okC = ld.issue_tile(stC);
     unsigned long long dsum[6] = {0, 0, 0, 0, 0, 0}, dt0 = 0, dt1 = 0, dsum6 = 0, dsum7 = 0;
 #pragma unroll 1
     for (int p = -1; p <= pend; ++p) {
@@ -985,7 +763,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_pp_bf16_kernel(const WgradA
         if ((p & 1) == grp) {
             const int k = p >> 1;
             if (k >= 0 && k < nk) {
-                multiply_tile(stC);
+                multiply_tile9<T3>(stC, abase, dbase4, acc);
                 char* tmp = stC; stC = stN; stN = tmp;
                 okC = okN;
                 role = 0;
@@ -996,13 +774,13 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_pp_bf16_kernel(const WgradA
             if (k < nk) {
                 const bool more = k + 1 < nk;
                 unsigned long long ta = 0, tb = 0;
-                if (more) okN = issue_tile(stN);
+                if (more) okN = ld.issue_tile(stN);
                 if constexpr (DIAG) ta = stamp_pp();
-                if (more) wait_all_but_one_tile();
+                if (more) wait_all_but_one_tile<T3>(ld.w4);
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if constexpr (DIAG) tb = stamp_pp();
-                load_consts(okC >> 16);
-                activate(stC, okC);
+                ld.load_consts(okC >> 16);
+                ld.activate(stC, okC);
                 role = 2;
                 if constexpr (DIAG) { dsum6 += tb - ta; dsum7 += ta - dt0; }
             }
@@ -1027,18 +805,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo_pp_bf16_kernel(const WgradA
             for (int r = 0; r < 16; ++r) red[((tap * 16 + r) * 4 + wave) * 64 + lane] = acc[tap][r];
     }
     __syncthreads();
-    if (grp == 0) {
-        float* slab = a.partials + (long)slice * 9 * a.Cin * a.Cout;
-        const int l31 = lane & 31, lh = lane >> 5;
-        const int ci = ci0 + wi * 32 + l31;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int co = co0 + wj * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            float* o = slab + ((long)co * a.Cin + ci) * 9;
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) o[tap] = acc[tap][r] + red[((tap * 16 + r) * 4 + wave) * 64 + lane];
-        }
-    }
+    if (grp == 0)
+        store_slab_oihw9<true>(a.partials + (long)b.slice * 9 * a.Cin * a.Cout, a.Cin, b.ci0 + wi * 32 + (lane & 31), b.co0 + wj * 32 + 4 * (lane >> 5), acc,
+                               red + wave * 64 + lane, 4 * 64);
 }
 
 }  // namespace
@@ -1091,7 +860,7 @@ int wgrad_halo_launch_bf16(const WgradArgs& a, int ksplit, int tiles_per, hipStr
     dim3 grid((a.Cin / 64) * (a.Cout / 64), ksplit), block(256);
     set_last_wgrad_variant(0x48000000 | (ksplit & 0xfff));
     if (a.src[0].pool) {
-        hipLaunchKernelGGL(wgrad_halo_bf16_kernel<true>, grid, block, 2 * ATILE + 2 * DTILE, st, a, a.Cout / 64, cdiv(a.Wb, TW), cdiv(a.Hb, TH), tiles_per);
+        hipLaunchKernelGGL(wgrad_halo_bf16_kernel, grid, block, 2 * ATILE + 2 * DTILE, st, a, a.Cout / 64, cdiv(a.Wb, TW), cdiv(a.Hb, TH), tiles_per);
     } else {
         WgradArgs b = a;
         b.ksplit = ksplit;

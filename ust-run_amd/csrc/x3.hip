@@ -636,17 +636,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3_kernel(const WgradArgs a, con
         cur = smem + (cur == smem ? WSTAGE2 : 0);
     }
 
-    // slab in the torch weight layout [Cout][Cin][3][3]
-    float* slab = a.partials + (long)blockIdx.y * 9 * a.Cin * a.Cout;
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int ci = ci0 + wi * 32 + l31;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int co = co0 + wj * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        float* o = slab + ((long)co * a.Cin + ci) * 9;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) o[tap] = acc[tap][r];
-    }
+    store_slab_oihw9(a.partials + (long)blockIdx.y * 9 * a.Cin * a.Cout, a.Cin, ci0 + wi * 32 + (lane & 31), co0 + wj * 32 + 4 * (lane >> 5), acc);
 }
 
 
