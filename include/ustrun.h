@@ -530,7 +530,8 @@ int ustrun_debug_conv_stat_rows(int N, int Ho, int Wo, int Cin, int Cout, int k,
  * bit 8 (256): no two-group weight-gradient kernel; bit 9 (512): ConvTranspose / 1x1 GEMM with weight tiles in LDS (round 2).
  * bits 10-11: force the halo kernel's tile in the 128-column case (1: 8 x 32 px, 2: 16 x 16, 3: 8 x 16; 0: chosen by padding).
  * bit 12 (4096): BatchNorm backward (plain, bf16) on the 4-channel-per-lane kernels instead of the 8-channel ones.
- * The last-variant code of the streaming kernel is 0x57530000 | (eight waves ? 0x100 : consumer / producer ? 0x200 : 0) | XF.
+ * The last-variant code of the streaming kernel is 0x57530000 | (eight waves ? 0x100 : consumer / producer ? 0x200 : 0) | XF, and on the
+ *   consumer / producer build | 0x400 with the BatchNorm-backward sums and | 0x800 on the flat plan (equal row steps per block).
  * The halo-tiled kernel runs plain sources (the input gradients) on its 256-pixel x 128-channel tiles on v_mfma_f32_16x16x32
  *   (ustrun_debug_last_conv_variant then carries bit 7, 0x80); bit 15 (32768): on every tile; bit 21 (2097152): on none.
  * bit 14 (16384): first convolution (C <= 4 -> 64) on the tile-per-block kernel of rounds 1-3 instead of the streaming one.

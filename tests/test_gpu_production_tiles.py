@@ -558,6 +558,8 @@ def test_wgrad_all_taps_builds_exact(case):
     # passes on a ragged map (9 row-steps in segments, 2.5 strips of 32 px)
     ("ws64_n8_128", 8, 2, 64, 64, 128, 128, "ws"),
     ("ws64_ragged", 16, 4, 64, 64, 72, 80, "ws"),
+    # the same build on the flat plan (260 strips of 8 steps -> 9 per block): sums of pieces cut mid-strip, the zero rows of uncut strips
+    ("ws64f_130_64", 130, 2, 64, 64, 64, 64, "wsf"),
 ])
 def test_input_gradient_with_batchnorm_backward_sums_exact(name, n, G, cin, cout, h, w, tile):
     """ustrun_conv3x3_dgrad_bnsum (round 4): the input gradient of a DoubleConv's second convolution IS da of the BatchNorm + ReLU
@@ -597,8 +599,8 @@ def test_input_gradient_with_batchnorm_backward_sums_exact(name, n, G, cin, cout
         assert rows.value == 0 and bool((dbuf == 9.0).all()) and bool((stat == 5.0).all()), "an unsupported shape must not launch"
         return
     assert rows.value > 0 and rows.value % G == 0 and rows.value <= rows_max
-    if tile == "ws":
-        assert lib.ustrun_debug_last_conv_variant() == 0x57530600, hex(lib.ustrun_debug_last_conv_variant())
+    if tile in ("ws", "wsf"):         # 'WS' | consumer/producer | sums, | 0x800 on the flat plan
+        assert lib.ustrun_debug_last_conv_variant() == {"ws": 0x57530600, "wsf": 0x57530E00}[tile], hex(lib.ustrun_debug_last_conv_variant())
     else:
         assert lib.ustrun_debug_last_conv_variant() == variant(*tile, False, False), vstr(lib.ustrun_debug_last_conv_variant())
     plain = torch.empty(n, h, w, cin, device="cuda", dtype=E.t)

@@ -21,13 +21,14 @@
 //     way out (fixed order, one partial row per wave and item).
 #include "common.h"
 #include "loader.h"
+#include "ws64_walk.h"
 #include <type_traits>
 
 namespace ustrun {
 namespace {
 
 
-constexpr int TW = 32, HW = TW + 2;
+constexpr int TW = WS_TW, HW = TW + 2;
 constexpr int PITCH = 144;                     // ring pixel: 64 channels + 16 B pad (conflict-free ds_read_b128 at any tap)
 constexpr int ROWB = HW * PITCH;               // 4896
 constexpr int BANKB = 8 * ROWB;                // 39168: one group of 8 input rows
@@ -37,23 +38,8 @@ constexpr int EWAVE = 128 * EPITCH;            // 10240 per wave (4 rows x 32 px
 constexpr int DUMMYB = 2048;                   // where threads 128..255 "write" the ninth staging item (2176 = 8.5 x 256)
 constexpr int LDSB = RINGB + 4 * EWAVE + DUMMYB;   // 160512 of 163840
 constexpr int GITEMS = 8 * HW * 8;             // 16-byte items of a group: 8 rows x 34 px x 8 channel octets = 2176
-constexpr int NR = (GITEMS + 255) / 256;       // staging rounds per group: 9 (the last one: waves 0 and 1 only)
-
-__device__ __attribute__((aligned(16))) const unsigned g_zero16w[4] = {0u, 0u, 0u, 0u};
-
-// Uniform plan: every strip is cut into sy segments of seg rows, item = (image, segment, strip), ipb items per block.
-// Flat plan (L > 0; the consumer / producer build only): the strips' 8-row steps form ONE sequence of N * sx * steps steps and
-// block b takes steps [b L, (b + 1) L) of it, whatever strips they fall in -- equal work per block at ANY image count (81 images of
-// 256^2: 648 strips over 256 CUs are 3 rounds of items with the last one half empty, but 81 steps per block exactly).  L >= steps,
-// so a strip is cut at most once: item slot = 2 strip + (the piece does not start at the strip's first row).
-struct WsPlan { int sx, sy, seg, items, ipb, L, steps; unsigned long long* dbg; };
 
 template <int V> using ic = std::integral_constant<int, V>;
-
-struct Cur {            // one group of 8 input rows of one item (or nothing)
-    int valid, item, img, x0, ybeg, S, k;
-    int left;           // flat plan: steps of the block's range behind this item
-};
 
 // One iteration u of a block's group sequence (groups = 8 input rows of an item, S + 1 per item):
 //   fetch  group u      -> registers (buffer loads: out-of-image items read as zero without touching memory)
@@ -76,6 +62,221 @@ __device__ __forceinline__ unsigned long long stamp() {
     return t;
 }
 
+// ======================================================================================================================
+// What the three builds below share (the plan and the cursors: ws64_walk.h).  Everything is force-inlined into its caller and every
+// array index is a constant at every call site, so each build keeps its own registers and its own schedule.
+
+// The block's (wave's) weights: KS = 4: A fragments of v_mfma_f32_32x32x16_bf16, k = 8 kq + j of the 16-channel step ks; KS = 2: of
+// v_mfma_f32_16x16x32_bf16, 32-channel steps.  row = the lane's output channel; packed layout [tap][Cin/8][Cout][8] -> one 16-byte
+// load each.  The input gradient walks the taps backwards (a.dstep < 0) over the [tap][Cout/8][Cin][8] pack.
+template <int KS>
+__device__ __forceinline__ void load_wfrags(bf16x8 (&Wr)[9][KS], const IgemmArgs& a, int kq, int row) {
+    const elt_t* Wp = (const elt_t*)a.W;
+    const bool wflip = a.dstep < 0;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const int wt = wflip ? 8 - tap : tap;
+            Wr[tap][ks] = *(const bf16x8*)(Wp + (((long)wt * 8 + (8 / KS) * ks + kq) * 64 + row) * 8);
+        }
+}
+
+// The row fetcher: THREADS threads (t = the thread's index among them) bring a group of 8 input rows of a strip into registers,
+// one iteration ahead, and write the previous group -- transformed -- into a ring bank of pixel pitch PITCHB.
+template <int THREADS, int PITCHB>
+struct RowFetch {
+    static constexpr int NR = (GITEMS + THREADS - 1) / THREADS;     // staging rounds per group (the last one: threads 0..127 only)
+    static constexpr int ROUNDB = THREADS / 8 * PITCHB;             // ring offset of item i: loff0 + i * ROUNDB
+    const SrcDev& S;
+    const __amdgpu_buffer_rsrc_t rs;
+    const int t, H, W, sH, sW;
+    // ---- staging geometry (the same for every group): item q = t + THREADS i of the group's [8 rows][34 px][8 octets] ----
+    int goffb[NR];         // byte offset from the group's first pixel
+    int rp[NR];            // row << 8 | pixel
+    int loff0;
+    int dummy;             // the last item exists for threads 0..127 only (2176 = 8.5 x 256): the others park theirs in a dummy region
+    char *wdst, *wlast;    // this iteration's ring bank (+ loff0), and where the last item goes
+    int in_soff;           // the fetched group's image, as the buffer loads' scalar offset
+    // ONE register set: item i of the group fetched last iteration is transformed and written to the ring in the second half
+    // of this iteration, and the same registers are refilled at once with item i of the next group -- every fetch gets exactly
+    // one iteration of flight
+    u32x4 stg[NR];
+    unsigned okmW = 0;             // in-image mask of the items held in stg
+    // byte offsets of group c's items inside its image (bit 31 set = beyond num_records: the buffer load returns zero without
+    // touching memory) and their in-image mask; computed in the shadow of the first half's MFMAs
+    unsigned offL[NR], okmL = 0;
+    unsigned xokm = 0;             // per item: its pixel column lies inside the image (changes with the item's strip only)
+    int xok_x0 = -(1 << 20);
+    f32x4 sc0 = {1.f, 1.f, 1.f, 1.f}, sc1 = sc0, sh0 = {0.f, 0.f, 0.f, 0.f}, sh1 = sh0;
+    const short a_floor16;         // ReLU on the rounded bf16 pairs (act8_bf16)
+
+    __device__ __forceinline__ RowFetch(const SrcDev& S_, __amdgpu_buffer_rsrc_t rs_, int t_, int H_, int W_, int dummy_)
+        : S(S_), rs(rs_), t(t_), H(H_), W(W_), sH((int)S_.sH), sW((int)S_.sW), dummy(dummy_), a_floor16(S_.relu ? (short)0 : (short)0x8000) {
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const int q = t + THREADS * i, hp = q >> 3, r = hp / HW, px = hp - r * HW;
+            goffb[i] = (r * sH + px * sW + (t & 7) * 8) * 2;
+            rp[i] = r << 8 | px;
+            stg[i] = (u32x4){0u, 0u, 0u, 0u};
+        }
+        loff0 = (t >> 3) * PITCHB + (t & 7) * 16;
+    }
+    // the iteration writes ring bank `bank` and fetches from the image at scalar offset soff
+    __device__ __forceinline__ void aim(char* bank, char* smem, int soff) {
+        wdst = bank + loff0;
+        wlast = t < 128 ? wdst + (NR - 1) * ROUNDB : smem + dummy;
+        in_soff = soff;
+    }
+    __device__ __forceinline__ void offsets_one(const Cur& c, int i) {
+        const int y0g = c.ybeg - 1 + 8 * c.k;
+        const int nrows = !c.valid ? 0 : (c.k == c.S ? 2 : 8);  // the item's last group: only its two halo rows are read
+        // rows of the group that exist: r < nrows and 0 <= y0g + r < H  (scalar: one 8-bit mask per group)
+        const int lo = max(0, -y0g), hi = min(nrows, H - y0g);
+        const unsigned ymask = hi > lo ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
+        const int gbase = (y0g * sH + (c.x0 - 1) * sW) * 2;
+        const unsigned ok = (ymask >> (rp[i] >> 8)) & (xokm >> i) & 1u;
+        offL[i] = (unsigned)(gbase + goffb[i]) | ((ok ^ 1u) << 31);      // (no select: hipcc turns it into an exec-masked branch)
+        okmL = (okmL & ~(1u << i)) | (ok << i);
+    }
+    __device__ __forceinline__ void xok_update(const Cur& c) {       // when the fetch cursor moves to another strip
+        if (c.x0 != xok_x0) {
+            xok_x0 = c.x0;
+            xokm = 0;
+#pragma unroll
+            for (int i = 0; i < NR; ++i)
+                xokm |= ((unsigned)(i < NR - 1 || t < 128) & (unsigned)((unsigned)(c.x0 - 1 + (rp[i] & 255)) < (unsigned)W)) << i;
+        }
+    }
+    // BatchNorm affine + ReLU in f32, back to bf16, zero padding applied after the activation
+    template <bool XF>
+    __device__ __forceinline__ u32x4 xform(u32x4 raw, bool ok) {
+        if constexpr (!XF) return raw;
+        u32x4 u = act8_bf16(raw, sc0, sc1, sh0, sh1, a_floor16);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) u[e] = ok ? u[e] : 0u;
+        return u;
+    }
+    template <bool XF>
+    __device__ __forceinline__ void load_consts(const Cur& c) {      // the pass constants of c's image, channel octet t & 7
+        if constexpr (XF) {
+            if (S.scale) {
+                const long go = S.gN > 0 ? (long)(c.img / S.gN) * S.gstride : 0;
+                const float* scp = S.scale + go + 8 * (t & 7);
+                const float* shp = S.shift + go + 8 * (t & 7);
+                sc0 = *(const f32x4*)scp; sc1 = *(const f32x4*)(scp + 4);
+                sh0 = *(const f32x4*)shp; sh1 = *(const f32x4*)(shp + 4);
+            }
+        }
+    }
+    template <bool XF>
+    __device__ __forceinline__ void stage(int i) {
+        *(u32x4*)(i < NR - 1 ? wdst + i * ROUNDB : wlast) = xform<XF>(stg[i], (okmW >> i) & 1u);
+        stg[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, offL[i], in_soff, 0);
+    }
+};
+
+// Ring addresses of the six patch rows 4 wm .. 4 wm + 5 of a step's 10 (8 in bank A = phase, 2 in bank B): wave row wm = 0 reads bank
+// A rows 0..5, wm = 1 bank A rows 4..7 and bank B rows 0, 1 -- two lane bases (frA, frB), the row picked by an immediate.
+template <int ROWBYTES, int BANKBYTES>
+__device__ __forceinline__ void ring_rows(int (&rowaddr)[6], int frA, int frB, bool hiB, int bA) {
+    const int bB = bA == 2 ? 0 : bA + 1;
+    rowaddr[0] = frA + bA * BANKBYTES; rowaddr[1] = rowaddr[0] + ROWBYTES; rowaddr[2] = rowaddr[0] + 2 * ROWBYTES; rowaddr[3] = rowaddr[0] + 3 * ROWBYTES;
+    rowaddr[4] = hiB ? frB + bB * BANKBYTES + 4 * ROWBYTES : frA + bA * BANKBYTES + 4 * ROWBYTES;
+    rowaddr[5] = rowaddr[4] + ROWBYTES;
+}
+
+// park two rows of 32x32x16 accumulators (bf16) in the wave's scratch, rows row0 and row0 + 1: lane = pixel, 4 consecutive channels
+// per register quad
+__device__ __forceinline__ void park_rows(char* Ew, int row0, const f32x16* acc2, int l31, int lh) {
+#pragma unroll
+    for (int ii = 0; ii < 2; ++ii) {
+        const int i = row0 + ii;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            bf16x4 h;
+            h[0] = (elt_t)acc2[ii][4 * g]; h[1] = (elt_t)acc2[ii][4 * g + 1];
+            h[2] = (elt_t)acc2[ii][4 * g + 2]; h[3] = (elt_t)acc2[ii][4 * g + 3];
+            *(bf16x4*)(Ew + (i * 32 + l31) * EPITCH + (8 * g + 4 * lh) * 2) = h;
+        }
+    }
+}
+
+// The lane that stores parked rows: lane (pp, o) stores pixel pp (+16) of a row, channel octet o of the wave's 32 channels
+struct PieceLane { int H, W, out_bytes, wm, pp, st_lane; };
+// byte offset of piece tt (row 2 HF + tt / 2 of the wave, pixel half tt & 1) of cursor c's step in the output (and in y: same
+// layout); bit 31 set -- and inimg false -- outside the image; `live`: the step exists (wave-uniform)
+__device__ __forceinline__ unsigned piece_off(const PieceLane& g, int HF, int tt, const Cur& c, bool live, bool& inimg) {
+    const int i = 2 * HF + (tt >> 1), px = 16 * (tt & 1) + g.pp;
+    const int y = c.ybeg + 8 * (c.k - 1) + 4 * g.wm + i;
+    const int ylim = min(c.ybeg + 8 * c.S, g.H);        // the item's rows (uniform plan: seg = 8 S but for an image's last segment)
+    inimg = live & (y < ylim) & (c.x0 + px < g.W);
+    return inimg ? (unsigned)(g.st_lane + (tt & 1) * 2048 + __builtin_amdgcn_readfirstlane(c.img * g.out_bytes + (y * g.W + c.x0) * 128)) : 0x80000000u;
+}
+
+// BatchNorm statistics of a stored piece (8 channels per lane): the sums see the stored values, zeros outside the image
+__device__ __forceinline__ void stat_add8(float (&s1)[8], float (&s2)[8], u32x4 u, bool inimg) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) u[e] = inimg ? u[e] : 0u;
+    const bf16x8 v = __builtin_bit_cast(bf16x8, u);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float f = (float)v[e];
+        s1[e] = add_scalar(s1[e], f);
+        s2[e] = fma_scalar(f, f, s2[e]);
+    }
+}
+// one partial row per (item, wm), this wave's 32 channels; zero_row (flat plan): a strip nobody cut -- its second slot's rows are zeros,
+// written here
+__device__ __forceinline__ void stat_flush8(float (&s1)[8], float (&s2)[8], float* stat, int item, int wm, int wn, int lane, bool zero_row) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+#pragma unroll
+        for (int d = 4; d < 64; d <<= 1) {
+            s1[e] += __shfl_xor(s1[e], d);
+            s2[e] += __shfl_xor(s2[e], d);
+        }
+    }
+    if (lane < 4) {
+        float* row = stat + ((long)(item * 2 + wm) * 2) * 64 + 32 * wn + 8 * lane;
+        *(f32x4*)row = (f32x4){s1[0], s1[1], s1[2], s1[3]};
+        *(f32x4*)(row + 4) = (f32x4){s1[4], s1[5], s1[6], s1[7]};
+        *(f32x4*)(row + 64) = (f32x4){s2[0], s2[1], s2[2], s2[3]};
+        *(f32x4*)(row + 68) = (f32x4){s2[4], s2[5], s2[6], s2[7]};
+        if (zero_row) {
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            float* row1 = row + 2 * 2 * 64;
+            *(f32x4*)row1 = z; *(f32x4*)(row1 + 4) = z; *(f32x4*)(row1 + 64) = z; *(f32x4*)(row1 + 68) = z;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
+}
+
+// The iteration with the ring phase m = u mod 3 a compile-time constant: the loop is unrolled three times, so that every LDS address
+// is a lane constant plus an immediate
+// (the lambdas by reference: taken by value, the four-wave build's cursors ended up in vector registers and its stores behind branches)
+template <class More, class Iter>
+__device__ __forceinline__ void ring_loop(const More& more, const Iter& iteration) {
+    while (true) {
+        if (!more()) break;
+        iteration(ic<0>{});
+        if (!more()) break;
+        iteration(ic<1>{});
+        if (!more()) break;
+        iteration(ic<2>{});
+    }
+}
+
+// DIAG builds: the wave's stamp sums -> p.dbg[slot = block * waves + wave][8]
+template <int K>
+__device__ __forceinline__ void diag_dump(unsigned long long* dbg, const unsigned long long (&dsum)[K], int lane, long slot) {
+    if (lane == 0 && dbg) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) dbg[slot * 8 + k] = dsum[k];
+    }
+}
+
 template <bool XF, bool STAT, bool DIAG = false>
 __global__ __launch_bounds__(256, 1) void conv3x3_ws64_kernel(const IgemmArgs a, const WsPlan p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -88,135 +289,41 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws64_kernel(const IgemmArgs a,
     const SrcDev S = a.src[0];
     const elt_t* srcp = (const elt_t*)S.ptr;
     const int H = a.Hb, W = a.Wb;
-    const int sH = (int)S.sH, sW = (int)S.sW;
     // one buffer descriptor per tensor (ws64_supported keeps them under 2 GiB); the image goes into the scalar offset
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)srcp, 0, (int)min((long)a.N * S.sN * 2, 0x7fffffffL), 0x00020000);
     const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)a.out0, 0, (int)min((long)a.N * H * W * 128, 0x7fffffffL), 0x00020000);
     const int img_bytes = (int)(S.sN * 2), out_bytes = H * W * 128;
 
     // ---- the block's weights: A fragments of v_mfma_f32_32x32x16_bf16, row = output channel 32 wn + l31, k = 8 lh + j
-    // of the 16-channel step ks; packed layout [tap][Cin/8][Cout][8] -> one 16-byte load each.  The input gradient
-    // walks the taps backwards (a.dstep < 0) over the [tap][Cout/8][Cin][8] pack. ----
+    // of the 16-channel step ks (load_wfrags) ----
     bf16x8 Wr[9][4];
-    {
-        const elt_t* Wp = (const elt_t*)a.W;
-        const bool wflip = a.dstep < 0;
+    load_wfrags(Wr, a, lh, 32 * wn + l31);
+    // A use in front of the loop: the compiler otherwise keeps these loads "pending" at the loop head and drains vmcnt(0)
+    // -- the row fetches in flight -- before the first MFMA of every iteration.  Constraint "a": the fragments live in
+    // the accumulator half of the register file, which MFMA reads directly; the 256 arch VGPRs stay free.
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap)
+    for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const int wt = wflip ? 8 - tap : tap;
-                Wr[tap][ks] = *(const bf16x8*)(Wp + (((long)wt * 8 + 2 * ks + lh) * 64 + 32 * wn + l31) * 8);
-            }
-        // A use in front of the loop: the compiler otherwise keeps these loads "pending" at the loop head and drains vmcnt(0)
-        // -- the row fetches in flight -- before the first MFMA of every iteration.  Constraint "a": the fragments live in
-        // the accumulator half of the register file, which MFMA reads directly; the 256 arch VGPRs stay free.
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+a"(Wr[tap][ks]));
-    }
+        for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+a"(Wr[tap][ks]));
 
-    // ---- staging geometry (the same for every group): item q = tid + 256 i of the group's [8 rows][34 px][8 octets] ----
-    int goffb[NR];         // byte offset from the group's first pixel
-    int rp[NR];            // row << 8 | pixel
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const int q = tid + 256 * i, hp = q >> 3, r = hp / HW, px = hp - r * HW;
-        goffb[i] = (r * sH + px * sW + (tid & 7) * 8) * 2;
-        rp[i] = r << 8 | px;
-    }
-    const int loff0 = (tid >> 3) * PITCH + (tid & 7) * 16;      // ring offset of item i: loff0 + i * 32 * PITCH
+    // ---- the row fetcher: all 256 threads; the ninth item exists for threads 0..127 only, the others park theirs in a dummy region ----
+    RowFetch<256, PITCH> rf(S, rs, tid, H, W, RINGB + 4 * EWAVE + (tid & 127) * 16);
+    static_assert(decltype(rf)::NR == 9, "the iteration below places nine staging items");
     const int afrag0 = l31 * PITCH + lh * 16;
-    // the ninth item exists for threads 0..127 only (2176 = 8.5 x 256): the others park theirs in a dummy region
-    const int wd8_dummy = RINGB + 4 * EWAVE + (tid & 127) * 16;
     // epilogue: lane (pp, o) stores pixel pp (+16) of a row, channel octet o of the wave's 32 channels
     const int pp = lane >> 2, o = lane & 3;
-    const int st_lane = (pp * 64 + 32 * wn + 8 * o) * 2;
+    const PieceLane pl = {H, W, out_bytes, wm, pp, (pp * 64 + 32 * wn + 8 * o) * 2};
 
     // ---- cursors over the block's sequence of groups: items [it0, it1), S + 1 groups each ----
     const int it0 = blockIdx.x * p.ipb, it1 = min(it0 + p.ipb, p.items);
-    auto decode = [&](int item, int k) __attribute__((always_inline)) {
-        Cur c;
-        c.valid = item < it1; c.k = k;
-        item = min(item, it1 - 1);                 // (geometry stays inside the tensor when there is nothing left)
-        c.item = item;
-        const int per = p.sx * p.sy;
-        c.img = item / per;
-        const int rem = item - c.img * per;
-        const int ys = rem / p.sx;
-        c.x0 = (rem - ys * p.sx) * TW;
-        c.ybeg = ys * p.seg;
-        const int rows = min(p.seg, H - c.ybeg);
-        c.S = (rows + 7) >> 3;
-        return c;
-    };
-    auto advance = [&](const Cur& c) __attribute__((always_inline)) {
-        if (!c.valid) return c;
-        if (c.k < c.S) { Cur n = c; n.k = c.k + 1; return n; }
-        return decode(c.item + 1, 0);
-    };
-    Cur cl = decode(it0, 0);
+    Cur cl = ws_decode(p, a.N, H, blockIdx.x, it1, it0, 0, false);
     Cur cw = cl, cc = cl, cp = cl;       // write / step / owed-half cursors, nothing there yet
     cw.valid = cc.valid = cp.valid = 0;
 
-    // ONE register set: item i of the group fetched last iteration is transformed and written to the ring in the second half
-    // of this iteration, and the same registers are refilled at once with item i of the next group -- every fetch gets exactly
-    // one iteration of flight
-    u32x4 stg[NR];
-    unsigned okmW = 0;             // in-image mask of the items held in stg
-#pragma unroll
-    for (int i = 0; i < NR; ++i) stg[i] = (u32x4){0u, 0u, 0u, 0u};
-    f32x4 sc0 = {1.f, 1.f, 1.f, 1.f}, sc1 = sc0, sh0 = {0.f, 0.f, 0.f, 0.f}, sh1 = sh0;
-    const short a_floor16 = S.relu ? (short)0 : (short)0x8000;     // ReLU on the rounded bf16 pairs (act8_bf16)
     float s1[8], s2[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
 
-    // byte offsets of group c's items inside its image (bit 31 set = beyond num_records: the buffer load returns zero without
-    // touching memory) and their in-image mask; computed in the shadow of the first half's MFMAs
-    unsigned offL[NR], okmL = 0;
-    unsigned xokm = 0;             // per item: its pixel column lies inside the image (changes with the item's strip only)
-    int xok_x0 = -1 << 20;
-    auto offsets_one = [&](const Cur& c, int i) __attribute__((always_inline)) {
-        const int y0g = c.ybeg - 1 + 8 * c.k;
-        const int nrows = !c.valid ? 0 : (c.k == c.S ? 2 : 8);  // the item's last group: only its two halo rows are read
-        // rows of the group that exist: r < nrows and 0 <= y0g + r < H  (scalar: one 8-bit mask per group)
-        const int lo = max(0, -y0g), hi = min(nrows, H - y0g);
-        const unsigned ymask = hi > lo ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
-        const int gbase = (y0g * sH + (c.x0 - 1) * sW) * 2;
-        const unsigned ok = (ymask >> (rp[i] >> 8)) & (xokm >> i) & 1u;
-        offL[i] = (unsigned)(gbase + goffb[i]) | ((ok ^ 1u) << 31);      // (no select: hipcc turns it into an exec-masked branch)
-        okmL = (okmL & ~(1u << i)) | (ok << i);
-    };
-    auto xok_update = [&](const Cur& c) __attribute__((always_inline)) {       // when the fetch cursor moves to another strip
-        if (c.x0 != xok_x0) {
-            xok_x0 = c.x0;
-            xokm = 0;
-#pragma unroll
-            for (int i = 0; i < NR; ++i)
-                xokm |= ((unsigned)(i < NR - 1 || tid < 128) & (unsigned)((unsigned)(c.x0 - 1 + (rp[i] & 255)) < (unsigned)W)) << i;
-        }
-    };
-    // BatchNorm affine + ReLU in f32, back to bf16, zero padding applied after the activation
-    auto xform = [&](u32x4 raw, bool ok) __attribute__((always_inline)) {
-        if constexpr (!XF) return raw;
-        u32x4 u = act8_bf16(raw, sc0, sc1, sh0, sh1, a_floor16);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) u[e] = ok ? u[e] : 0u;
-        return u;
-    };
-    auto load_consts = [&](const Cur& c) __attribute__((always_inline)) {      // the pass constants of c's image, channel octet tid & 7
-        if constexpr (XF) {
-            if (S.scale) {
-                const long go = S.gN > 0 ? (long)(c.img / S.gN) * S.gstride : 0;
-                const float* scp = S.scale + go + 8 * (tid & 7);
-                const float* shp = S.shift + go + 8 * (tid & 7);
-                sc0 = *(const f32x4*)scp; sc1 = *(const f32x4*)(scp + 4);
-                sh0 = *(const f32x4*)shp; sh1 = *(const f32x4*)(shp + 4);
-            }
-        }
-    };
 
     // ---- the step in two halves of the wave's four rows (HALF 0: rows 0, 1 from patch rows 0..3; HALF 1: rows 2, 3 from
     // patch rows 2..5): the epilogue of one half runs under the MFMAs of the other, across the iteration boundary for
@@ -254,93 +361,44 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws64_kernel(const IgemmArgs a,
     // a wave's instructions in order, so the scratch needs no barrier between A and B.
     auto epi_A = [&](auto half_c) __attribute__((always_inline)) {
         constexpr int HF = decltype(half_c)::value;
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii) {
-            const int i = 2 * HF + ii;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                bf16x4 h;
-                h[0] = (elt_t)acc[i][4 * g]; h[1] = (elt_t)acc[i][4 * g + 1];
-                h[2] = (elt_t)acc[i][4 * g + 2]; h[3] = (elt_t)acc[i][4 * g + 3];
-                *(bf16x4*)(Ew + (i * 32 + l31) * EPITCH + (8 * g + 4 * lh) * 2) = h;
-            }
-        }
+        park_rows(Ew, 2 * HF, &acc[2 * HF], l31, lh);
     };
     // tt = 0..3: row 2 HF + tt / 2 of the wave, pixel half tt & 1; `live`: the step exists (wave-uniform)
     auto epi_B = [&](auto half_c, int tt, const Cur& c, bool live) __attribute__((always_inline)) {
         constexpr int HF = decltype(half_c)::value;
         const int i = 2 * HF + (tt >> 1), px = 16 * (tt & 1) + pp;
-        const int y = c.ybeg + 8 * (c.k - 1) + 4 * wm + i;
-        const int ylim = min(c.ybeg + p.seg, H);
         u32x4 u = *(const u32x4*)(Ew + (i * 32 + px) * EPITCH + o * 16);
-        const bool inimg = live & (y < ylim) & (c.x0 + px < W);
+        bool inimg;
         // (the row offset is added into the VECTOR offset and soffset stays 0: for a 128-bit buffer store with an SGPR soffset hipcc's
         // hazard recognizer inserts no wait state in front of a VALU write of the store's data registers -- the selects right below --
         // and gfx950 then ships the overwritten dword under store pressure: found in conv_first.hip, round 4)
-        const unsigned voff = inimg ? (unsigned)(st_lane + (tt & 1) * 2048 + __builtin_amdgcn_readfirstlane(c.img * out_bytes + (y * W + c.x0) * 128)) : 0x80000000u;
+        const unsigned voff = piece_off(pl, HF, tt, c, live, inimg);
         __builtin_amdgcn_raw_buffer_store_b128(u, ro, voff, 0, 0);
-        if constexpr (STAT) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) u[e] = inimg ? u[e] : 0u;
-            const bf16x8 v = __builtin_bit_cast(bf16x8, u);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float f = (float)v[e];           // statistics see the stored values
-                s1[e] = add_scalar(s1[e], f);
-                s2[e] = fma_scalar(f, f, s2[e]);
-            }
-        }
+        if constexpr (STAT) stat_add8(s1, s2, u, inimg);          // statistics see the stored values
     };
     auto stat_flush = [&](const Cur& c) __attribute__((always_inline)) {       // one partial row per (item, wm), this wave's 32 channels
-        if constexpr (STAT) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-#pragma unroll
-                for (int d = 4; d < 64; d <<= 1) {
-                    s1[e] += __shfl_xor(s1[e], d);
-                    s2[e] += __shfl_xor(s2[e], d);
-                }
-            }
-            if (lane < 4) {
-                float* row = a.stat + ((long)(c.item * 2 + wm) * 2) * 64 + 32 * wn + 8 * lane;
-                *(f32x4*)row = (f32x4){s1[0], s1[1], s1[2], s1[3]};
-                *(f32x4*)(row + 4) = (f32x4){s1[4], s1[5], s1[6], s1[7]};
-                *(f32x4*)(row + 64) = (f32x4){s2[0], s2[1], s2[2], s2[3]};
-                *(f32x4*)(row + 68) = (f32x4){s2[4], s2[5], s2[6], s2[7]};
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
-        }
+        if constexpr (STAT) stat_flush8(s1, s2, a.stat, c.item, wm, wn, lane, false);
     };
+
 
     unsigned long long dsum[6] = {0, 0, 0, 0, 0, 0}, dt0 = 0, dt1 = 0;
     bool pend = false;     // the previous iteration ran a step: the epilogue of its second half is owed (cursor cp)
-    load_consts(cl);
-    // The iteration, with the ring phase m = u mod 3 a compile-time constant (the loop below is unrolled three times): the step
-    // reads banks m and m + 1, the write goes to bank m + 2, and every LDS address is a lane constant plus an immediate.
-    // Patch rows 4 wm .. 4 wm + 5 of the step's 10 (8 in bank A, 2 in bank B): wave row wm = 0 reads bank A rows 0..5, wm = 1
-    // bank A rows 4..7 and bank B rows 0, 1 -- two lane bases, the row picked by an immediate.
+    rf.load_consts<XF>(cl);
+    // The iteration, with the ring phase m = u mod 3 a compile-time constant (ring_loop): the step reads banks m and m + 1 (ring_rows),
+    // the write goes to bank m + 2, and every LDS address is a lane constant plus an immediate.
     const int frA = afrag0 + 4 * wm * ROWB;                       // + bank A * BANKB + q * ROWB          (q < 4 or wm == 0)
     const int frB = afrag0 + (4 * wm - 8) * ROWB;                 // + bank B * BANKB + q * ROWB          (q >= 4 and wm == 1)
     const bool hiB = wm == 1;
     auto iteration = [&](auto m_c) __attribute__((always_inline)) {
-        constexpr int bA = decltype(m_c)::value, bB = bA == 2 ? 0 : bA + 1, bW = bA == 0 ? 2 : bA - 1;
+        constexpr int bA = decltype(m_c)::value, bW = bA == 0 ? 2 : bA - 1;
         const bool live = cc.valid && cc.k >= 1;
-        rowaddr[0] = frA + bA * BANKB; rowaddr[1] = rowaddr[0] + ROWB; rowaddr[2] = rowaddr[0] + 2 * ROWB; rowaddr[3] = rowaddr[0] + 3 * ROWB;
-        rowaddr[4] = hiB ? frB + bB * BANKB + 4 * ROWB : frA + bA * BANKB + 4 * ROWB;
-        rowaddr[5] = rowaddr[4] + ROWB;
-        char* wdst = ring + bW * BANKB + loff0;
-        char* wd8 = tid < 128 ? wdst + 8 * (32 * PITCH) : smem + wd8_dummy;
-        const Cur cn = advance(cl);
-        xok_update(cl);
-        const int in_soff = __builtin_amdgcn_readfirstlane(cl.img * img_bytes);
+        ring_rows<ROWB, BANKB>(rowaddr, frA, frB, hiB, decltype(m_c)::value);
+        const Cur cn = ws_advance_div(p, a.N, H, blockIdx.x, it1, cl);
+        rf.xok_update(cl);
+        rf.aim(ring + bW * BANKB, smem, __builtin_amdgcn_readfirstlane(cl.img * img_bytes));
         // 24 groups (half, dx, ks) of 4 fragment reads + 6 MFMAs in one stream; the reads run TWO groups ahead of their MFMAs
         // (one group = 192 MFMA cycles is less than an LDS round trip with four waves reading and writing)
         bf16x8 pf[3][4];
-        auto stage = [&](int i) __attribute__((always_inline)) {
-            *(u32x4*)(i < NR - 1 ? wdst + i * (32 * PITCH) : wd8) = xform(stg[i], (okmW >> i) & 1u);
-            stg[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, offL[i], in_soff, 0);
-        };
         auto read_group = [&](int gg) __attribute__((always_inline)) {       // gg = 0..23, folds to a constant
             if (gg < 12) frag_read(ic<0>{}, gg / 4, gg % 4, pf[gg % 3]);
             else if (gg < 24) frag_read(ic<1>{}, (gg - 12) / 4, (gg - 12) % 4, pf[gg % 3]);
@@ -354,17 +412,17 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws64_kernel(const IgemmArgs a,
             read_group(g + 2);
             mma6(ic<0>{}, g / 4, g % 4, pf[g % 3]);
             if (g == 0) epi_A(ic<1>{});
-            if (g == 1) offsets_one(cl, 0);
-            if (g == 2) offsets_one(cl, 1);
+            if (g == 1) rf.offsets_one(cl, 0);
+            if (g == 2) rf.offsets_one(cl, 1);
             if (g == 3) epi_B(ic<1>{}, 0, cp, pend);
-            if (g == 4) offsets_one(cl, 2);
+            if (g == 4) rf.offsets_one(cl, 2);
             if (g == 5) epi_B(ic<1>{}, 1, cp, pend);
-            if (g == 6) offsets_one(cl, 3);
+            if (g == 6) rf.offsets_one(cl, 3);
             if (g == 7) epi_B(ic<1>{}, 2, cp, pend);
-            if (g == 8) { offsets_one(cl, 4); offsets_one(cl, 5); }
+            if (g == 8) { rf.offsets_one(cl, 4); rf.offsets_one(cl, 5); }
             if (g == 9) epi_B(ic<1>{}, 3, cp, pend);
-            if (g == 10) { offsets_one(cl, 6); offsets_one(cl, 7); }
-            if (g == 11) offsets_one(cl, 8);
+            if (g == 10) { rf.offsets_one(cl, 6); rf.offsets_one(cl, 7); }
+            if (g == 11) rf.offsets_one(cl, 8);
         }
         // between the halves: half 0 of THIS step adds to the sums next
         if (pend && cp.k == cp.S) stat_flush(cp);
@@ -377,19 +435,19 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws64_kernel(const IgemmArgs a,
             read_group(12 + g + 2);
             mma6(ic<1>{}, g / 4, g % 4, pf[(12 + g) % 3]);
             if (g == 0) epi_A(ic<0>{});
-            if (g == 1) stage(0);
-            if (g == 2) stage(1);
+            if (g == 1) rf.stage<XF>(0);
+            if (g == 2) rf.stage<XF>(1);
             if (g == 3) epi_B(ic<0>{}, 0, cc, live);
-            if (g == 4) stage(2);
-            if (g == 5) { epi_B(ic<0>{}, 1, cc, live); stage(3); }
-            if (g == 6) stage(4);
-            if (g == 7) { epi_B(ic<0>{}, 2, cc, live); stage(5); }
-            if (g == 8) stage(6);
-            if (g == 9) { epi_B(ic<0>{}, 3, cc, live); stage(7); }
-            if (g == 10) stage(8);
+            if (g == 4) rf.stage<XF>(2);
+            if (g == 5) { epi_B(ic<0>{}, 1, cc, live); rf.stage<XF>(3); }
+            if (g == 6) rf.stage<XF>(4);
+            if (g == 7) { epi_B(ic<0>{}, 2, cc, live); rf.stage<XF>(5); }
+            if (g == 8) rf.stage<XF>(6);
+            if (g == 9) { epi_B(ic<0>{}, 3, cc, live); rf.stage<XF>(7); }
+            if (g == 10) rf.stage<XF>(8);
         }
-        okmW = okmL;
-        load_consts(cl);          // for the group fetched above (queued behind its rows; used next iteration)
+        rf.okmW = rf.okmL;
+        rf.load_consts<XF>(cl);          // for the group fetched above (queued behind its rows; used next iteration)
         if constexpr (DIAG) { dt1 = stamp(); dsum[2] += dt1 - dt0; dt0 = dt1; dsum[5] += 1; }
         // the ring bank written above is read from the next iteration on; the scratch is private to the wave
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -399,22 +457,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws64_kernel(const IgemmArgs a,
         cp = cc; pend = live;
         cc = cw; cw = cl; cl = cn;
     };
-    while (true) {
-        if (!(cl.valid | cw.valid | cc.valid | (int)pend)) break;
-        iteration(ic<0>{});
-        if (!(cl.valid | cw.valid | cc.valid | (int)pend)) break;
-        iteration(ic<1>{});
-        if (!(cl.valid | cw.valid | cc.valid | (int)pend)) break;
-        iteration(ic<2>{});
-    }
-    if constexpr (DIAG) {
-        if (lane == 0 && p.dbg) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) p.dbg[((long)blockIdx.x * 4 + wave) * 8 + k] = dsum[k];
-        }
-    }
+    ring_loop([&]() { return (cl.valid | cw.valid | cc.valid | (int)pend) != 0; }, iteration);
+    if constexpr (DIAG) diag_dump(p.dbg, dsum, lane, (long)blockIdx.x * 4 + wave);
 }
-
 
 // ======================================================================================================================
 // Round 3: the same streaming structure on EIGHT waves (two per SIMD) -- conv3x3_ws64x8_kernel.
@@ -455,32 +500,24 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64x8_kernel(const IgemmArgs 
     const SrcDev S = a.src[0];
     const elt_t* srcp = (const elt_t*)S.ptr;
     const int H = a.Hb, W = a.Wb;
-    const int sH = (int)S.sH, sW = (int)S.sW;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)srcp, 0, (int)min((long)a.N * S.sN * 2, 0x7fffffffL), 0x00020000);
     const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)a.out0, 0, (int)min((long)a.N * H * W * 128, 0x7fffffffL), 0x00020000);
     const int img_bytes = (int)(S.sN * 2), out_bytes = H * W * 128;
 
     // ---- the wave's weights: A fragments of v_mfma_f32_16x16x32_bf16, row = output channel 16 cg + lp, k = 8 lq + j of the
-    // 32-channel step ks; packed layout [tap][Cin/8][Cout][8] -> one 16-byte load each (input gradient: taps backwards over
-    // the [tap][Cout/8][Cin][8] pack) ----
+    // 32-channel step ks (load_wfrags) ----
     bf16x8 Wr[9][2];
-    {
-        const elt_t* Wp = (const elt_t*)a.W;
-        const bool wflip = a.dstep < 0;
+    load_wfrags(Wr, a, lq, 16 * cg + lp);
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap)
+    for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const int wt = wflip ? 8 - tap : tap;
-                Wr[tap][ks] = *(const bf16x8*)(Wp + (((long)wt * 8 + 4 * ks + lq) * 64 + 16 * cg + lp) * 8);
-            }
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) asm volatile("" : "+v"(Wr[tap][ks]));       // (loaded before the loop, not pending at its head)
-    }
+        for (int ks = 0; ks < 2; ++ks) asm volatile("" : "+v"(Wr[tap][ks]));       // (loaded before the loop, not pending at its head)
 
-    // ---- staging geometry: item q = tid + 512 i of the group's [8 rows][34 px][8 octets] ----
+    // ---- the row fetch, as RowFetch<512, PITCH8> would do it, kept in lambdas here: this build sits AT its 256 registers and spills
+    // (up to 24 dwords), and on the struct -- or with ring_rows / ring_loop -- hipcc's allocation shifts by a few dwords, in
+    // some instantiations upwards (7 -> 9, 23 -> 26); with the code below every instantiation keeps its registers and its spill ----
+    const int sH = (int)S.sH, sW = (int)S.sW;
+    // staging geometry: item q = tid + 512 i of the group's [8 rows][34 px][8 octets]
     int goffb[NR8], rp[NR8];
 #pragma unroll
     for (int i = 0; i < NR8; ++i) {
@@ -494,27 +531,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64x8_kernel(const IgemmArgs 
     const int st_lane = lp * 128 + 32 * cg + 8 * lq;             // output byte offset of the lane's 4 channels inside a 16-px run
 
     const int it0 = blockIdx.x * p.ipb, it1 = min(it0 + p.ipb, p.items);
-    auto decode = [&](int item, int k) __attribute__((always_inline)) {
-        Cur c;
-        c.valid = item < it1; c.k = k;
-        item = min(item, it1 - 1);
-        c.item = item;
-        const int per = p.sx * p.sy;
-        c.img = item / per;
-        const int rem = item - c.img * per;
-        const int ys = rem / p.sx;
-        c.x0 = (rem - ys * p.sx) * TW;
-        c.ybeg = ys * p.seg;
-        const int rows = min(p.seg, H - c.ybeg);
-        c.S = (rows + 7) >> 3;
-        return c;
-    };
-    auto advance = [&](const Cur& c) __attribute__((always_inline)) {
-        if (!c.valid) return c;
-        if (c.k < c.S) { Cur n = c; n.k = c.k + 1; return n; }
-        return decode(c.item + 1, 0);
-    };
-    Cur cl = decode(it0, 0);
+    Cur cl = ws_decode(p, a.N, H, blockIdx.x, it1, it0, 0, false);
     Cur cw = cl, cc = cl;                // write / step cursors, nothing there yet
     cw.valid = cc.valid = 0;
 
@@ -524,8 +541,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64x8_kernel(const IgemmArgs 
     for (int i = 0; i < NR8; ++i) stg[i] = (u32x4){0u, 0u, 0u, 0u};
     f32x4 sc0 = {1.f, 1.f, 1.f, 1.f}, sc1 = sc0, sh0 = {0.f, 0.f, 0.f, 0.f}, sh1 = sh0;
     const short a_floor16 = S.relu ? (short)0 : (short)0x8000;     // ReLU on the rounded bf16 pairs (act8_bf16)
-    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-
     unsigned offL[NR8], okmL = 0;
     unsigned xokm = 0;
     int xok_x0 = -(1 << 20);
@@ -566,6 +581,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64x8_kernel(const IgemmArgs 
             }
         }
     };
+    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
 
     f32x4 acc[4][2];                     // [output row of the wave][pixel half]: 16 channels x 16 pixels each
     int rowaddr[6];
@@ -627,14 +643,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64x8_kernel(const IgemmArgs 
     const int frB = afrag0 + (4 * wm - 8) * ROWB8;                // + bank B * BANKB8 + q * ROWB8          (q >= 4 and wm == 1)
     const bool hiB = wm == 1;
     auto iteration = [&](auto m_c) __attribute__((always_inline)) {
-        constexpr int bA = decltype(m_c)::value, bB = bA == 2 ? 0 : bA + 1, bW = bA == 0 ? 2 : bA - 1;
+        constexpr int bA = decltype(m_c)::value, bW = bA == 0 ? 2 : bA - 1;
         const bool live = cc.valid && cc.k >= 1;
+        constexpr int bB = bA == 2 ? 0 : bA + 1;
         rowaddr[0] = frA + bA * BANKB8; rowaddr[1] = rowaddr[0] + ROWB8; rowaddr[2] = rowaddr[0] + 2 * ROWB8; rowaddr[3] = rowaddr[0] + 3 * ROWB8;
         rowaddr[4] = hiB ? frB + bB * BANKB8 + 4 * ROWB8 : frA + bA * BANKB8 + 4 * ROWB8;
         rowaddr[5] = rowaddr[4] + ROWB8;
+        const Cur cn = ws_advance_div(p, a.N, H, blockIdx.x, it1, cl);
         char* wdst = ring + bW * BANKB8 + loff0;
         char* wd4 = tid < 128 ? wdst + 4 * (64 * PITCH8) : smem + wd4_dummy;
-        const Cur cn = advance(cl);
         xok_update(cl);
         const int in_soff = __builtin_amdgcn_readfirstlane(cl.img * img_bytes);
         bf16x8 pf[2][6];
@@ -691,12 +708,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64x8_kernel(const IgemmArgs 
         if (!(cl.valid | cw.valid | cc.valid)) break;
         iteration(ic<2>{});
     }
-    if constexpr (DIAG) {
-        if (lane == 0 && p.dbg) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) p.dbg[((long)blockIdx.x * 8 + wave) * 8 + k] = dsum[k];
-        }
-    }
+    if constexpr (DIAG) diag_dump(p.dbg, dsum, lane, (long)blockIdx.x * 8 + wave);
 }
 
 
@@ -744,7 +756,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64cp_kernel(const IgemmArgs 
     const SrcDev S = a.src[0];
     const elt_t* srcp = (const elt_t*)S.ptr;
     const int H = a.Hb, W = a.Wb;
-    const int sH = (int)S.sH, sW = (int)S.sW;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)srcp, 0, (int)min((long)a.N * S.sN * 2, 0x7fffffffL), 0x00020000);
     const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)a.out0, 0, (int)min((long)a.N * H * W * 128, 0x7fffffffL), 0x00020000);
     const int img_bytes = (int)(S.sN * 2), out_bytes = H * W * 128;
@@ -752,68 +763,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64cp_kernel(const IgemmArgs 
     // ---- cursors over the block's sequence of groups (all eight waves keep them: the trip count must agree) ----
     const bool flat = p.L > 0;
     const int it0 = blockIdx.x * p.ipb, it1 = min(it0 + p.ipb, p.items);
-    auto decode = [&](int item, int k) __attribute__((always_inline)) {
-        Cur c;
-        c.k = k; c.left = 0;
-        if (flat) {             // the block's first piece: wherever step blockIdx.x * L falls
-            const int total = a.N * p.sx * p.steps;
-            const int pos = blockIdx.x * p.L, end = min(pos + p.L, total);
-            const int strip = pos / p.steps, st = pos - strip * p.steps;
-            c.valid = pos < end;
-            c.img = strip / p.sx;
-            c.x0 = (strip - c.img * p.sx) * TW;
-            c.ybeg = st * 8;
-            c.S = max(min(p.steps - st, end - pos), 1);
-            c.left = max(end - pos - c.S, 0);
-            c.item = strip * 2 + (st != 0 ? 1 : 0);
-            return c;
-        }
-        c.valid = item < it1;
-        item = min(item, it1 - 1);
-        c.item = item;
-        const int per = p.sx * p.sy;
-        c.img = item / per;
-        const int rem = item - c.img * per;
-        const int ys = rem / p.sx;
-        c.x0 = (rem - ys * p.sx) * TW;
-        c.ybeg = ys * p.seg;
-        const int rows = min(p.seg, H - c.ybeg);
-        c.S = (rows + 7) >> 3;
-        return c;
-    };
-    // the next group: same item, or the next item by counting (strip, segment, image) up -- no divisions on the producers'
-    // path between two barriers (the division-based decode runs once, for the block's first item)
-    auto advance = [&](const Cur& c) __attribute__((always_inline)) {
-        Cur n = c;
-        const bool same = c.k < c.S;
-        if (flat) {             // the next piece starts at the next strip's first row and ends with the strip or with the block's range
-            const bool has = c.left > 0;
-            int x0 = c.x0 + TW, img = c.img;
-            const bool wrapx = x0 >= p.sx * TW;
-            x0 = wrapx ? 0 : x0;
-            img = wrapx ? img + 1 : img;
-            const int S = min(p.steps, c.left);
-            if (same) n.k = c.k + 1;
-            else if (has) { n.item = (c.item | 1) + 1; n.img = img; n.x0 = x0; n.ybeg = 0; n.S = S; n.left = c.left - S; n.k = 0; }
-            else { n.valid = 0; n.k = 0; }
-            return c.valid ? n : c;
-        }
-        const int item = min(c.item + 1, it1 - 1);
-        const bool has = c.item + 1 < it1;
-        int x0 = c.x0 + TW, ybeg = c.ybeg, img = c.img;
-        const bool wrapx = x0 >= p.sx * TW;
-        x0 = wrapx ? 0 : x0;
-        ybeg = wrapx ? ybeg + p.seg : ybeg;
-        const bool wrapy = ybeg >= p.sy * p.seg;
-        ybeg = wrapy ? 0 : ybeg;
-        img = wrapy ? img + 1 : img;
-        const int rows = min(p.seg, H - ybeg);
-        if (same) n.k = c.k + 1;
-        else if (has) { n.item = item; n.img = img; n.x0 = x0; n.ybeg = ybeg; n.S = (rows + 7) >> 3; n.k = 0; }
-        else { n.valid = 0; n.k = 0; }
-        return c.valid ? n : c;
-    };
-    Cur cl = decode(it0, 0);
+    Cur cl = ws_decode(p, a.N, H, blockIdx.x, it1, it0, 0, flat);
     Cur cw = cl, cc = cl, cp = cl;
     cw.valid = cc.valid = cp.valid = 0;
     bool pend = false;
@@ -825,21 +775,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64cp_kernel(const IgemmArgs 
     if (!producer) {
         // =================================== consumer ===================================
         bf16x8 Wr[9][4];
-        {
-            const elt_t* Wp = (const elt_t*)a.W;
-            const bool wflip = a.dstep < 0;
+        load_wfrags(Wr, a, lh, 32 * wn + l31);
 #pragma unroll
-            for (int tap = 0; tap < 9; ++tap)
+        for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const int wt = wflip ? 8 - tap : tap;
-                    Wr[tap][ks] = *(const bf16x8*)(Wp + (((long)wt * 8 + 2 * ks + lh) * 64 + 32 * wn + l31) * 8);
-                }
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(Wr[tap][ks]));
-        }
+            for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(Wr[tap][ks]));
         int rowaddr[6];
         f32x16 acc[2];
         // (reading the next half-step's first two fragment groups across the barrier -- legal: they only touch ring rows complete
@@ -865,25 +805,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64cp_kernel(const IgemmArgs 
                     for (int dy = 0; dy < 3; ++dy)       // (the first product of an accumulator takes the constant 0 as C: no zeroing pass)
                         acc[i] = USTRUN_MFMA_32x32x16(Wr[dy * 3 + g / 4][g % 4], pf[g % 3][i + dy], (g == 0 && dy == 0) ? zero16 : acc[i], 0, 0, 0);
             }
-            // park the half's rows (bf16) in the wave's scratch: lane = pixel, 4 consecutive channels per register quad
-#pragma unroll
-            for (int ii = 0; ii < 2; ++ii) {
-                const int i = 2 * HF + ii;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    bf16x4 h;
-                    h[0] = (elt_t)acc[ii][4 * g]; h[1] = (elt_t)acc[ii][4 * g + 1];
-                    h[2] = (elt_t)acc[ii][4 * g + 2]; h[3] = (elt_t)acc[ii][4 * g + 3];
-                    *(bf16x4*)(Ew + (i * 32 + l31) * EPITCH + (8 * g + 4 * lh) * 2) = h;
-                }
-            }
+            // park the half's rows (bf16) in the wave's scratch
+            park_rows(Ew, 2 * HF, acc, l31, lh);
         };
         auto iteration = [&](auto m_c) __attribute__((always_inline)) {
-            constexpr int bA = decltype(m_c)::value, bB = bA == 2 ? 0 : bA + 1;
-            rowaddr[0] = frA + bA * BANKB; rowaddr[1] = rowaddr[0] + ROWB; rowaddr[2] = rowaddr[0] + 2 * ROWB; rowaddr[3] = rowaddr[0] + 3 * ROWB;
-            rowaddr[4] = hiB ? frB + bB * BANKB + 4 * ROWB : frA + bA * BANKB + 4 * ROWB;
-            rowaddr[5] = rowaddr[4] + ROWB;
-            const Cur cn = advance(cl);
+            ring_rows<ROWB, BANKB>(rowaddr, frA, frB, hiB, decltype(m_c)::value);
+            const Cur cn = ws_advance(p, H, it1, cl, flat);
             if constexpr (DIAG) dt0 = stamp();
             half(ic<0>{});
             if constexpr (DIAG) { dt1 = stamp(); dsum[0] += dt1 - dt0; dt0 = dt1; }
@@ -900,41 +827,16 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64cp_kernel(const IgemmArgs 
             cp = cc; pend = cc.valid && cc.k >= 1;
             cc = cw; cw = cl; cl = cn;
         };
-        while (true) {
-            if (!(cl.valid | cw.valid | cc.valid | (int)pend)) break;
-            iteration(ic<0>{});
-            if (!(cl.valid | cw.valid | cc.valid | (int)pend)) break;
-            iteration(ic<1>{});
-            if (!(cl.valid | cw.valid | cc.valid | (int)pend)) break;
-            iteration(ic<2>{});
-        }
-        if constexpr (DIAG) {
-            if (lane == 0 && p.dbg) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) p.dbg[((long)blockIdx.x * 8 + wave8) * 8 + k] = dsum[k];
-            }
-        }
+        ring_loop([&]() { return (cl.valid | cw.valid | cc.valid | (int)pend) != 0; }, iteration);
+        if constexpr (DIAG) diag_dump(p.dbg, dsum, lane, (long)blockIdx.x * 8 + wave8);
         return;
     }
 
     // =================================== producer ===================================
-    int goffb[NR], rp[NR];
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const int q = tp + 256 * i, hp = q >> 3, r = hp / HW, px = hp - r * HW;
-        goffb[i] = (r * sH + px * sW + (tp & 7) * 8) * 2;
-        rp[i] = r << 8 | px;
-    }
-    const int loff0 = (tp >> 3) * PITCH + (tp & 7) * 16;
-    const int wd8_dummy = RINGB + 4 * EWAVE + (tp & 127) * 16;
+    // the row fetcher: the four producer waves, as the four-wave kernel's 256 threads
+    RowFetch<256, PITCH> rf(S, rs, tp, H, W, RINGB + 4 * EWAVE + (tp & 127) * 16);
     const int pp = lane >> 2, o = lane & 3;
-    const int st_lane = (pp * 64 + 32 * wn + 8 * o) * 2;
-    u32x4 stg[NR];
-    unsigned okmW = 0;
-#pragma unroll
-    for (int i = 0; i < NR; ++i) stg[i] = (u32x4){0u, 0u, 0u, 0u};
-    f32x4 sc0 = {1.f, 1.f, 1.f, 1.f}, sc1 = sc0, sh0 = {0.f, 0.f, 0.f, 0.f}, sh1 = sh0;
-    const short a_floor16 = S.relu ? (short)0 : (short)0x8000;     // ReLU on the rounded bf16 pairs (act8_bf16)
+    const PieceLane pl = {H, W, out_bytes, wm, pp, (pp * 64 + 32 * wn + 8 * o) * 2};
     float s1[8], s2[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
@@ -959,63 +861,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64cp_kernel(const IgemmArgs 
             for (int e = 0; e < 4; ++e) { bsc[set][e] = x0[e]; bsc[set][4 + e] = x1[e]; bsh[set][e] = b0[e]; bsh[set][4 + e] = b1[e]; }
         }
     };
-    unsigned offL[NR], okmL = 0;
-    unsigned xokm = 0;
-    int xok_x0 = -(1 << 20);
-    auto offsets_one = [&](const Cur& c, int i) __attribute__((always_inline)) {
-        const int y0g = c.ybeg - 1 + 8 * c.k;
-        const int nrows = !c.valid ? 0 : (c.k == c.S ? 2 : 8);
-        const int lo = max(0, -y0g), hi = min(nrows, H - y0g);
-        const unsigned ymask = hi > lo ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
-        const int gbase = (y0g * sH + (c.x0 - 1) * sW) * 2;
-        const unsigned ok = (ymask >> (rp[i] >> 8)) & (xokm >> i) & 1u;
-        offL[i] = (unsigned)(gbase + goffb[i]) | ((ok ^ 1u) << 31);
-        okmL = (okmL & ~(1u << i)) | (ok << i);
-    };
-    auto xok_update = [&](const Cur& c) __attribute__((always_inline)) {
-        if (c.x0 != xok_x0) {
-            xok_x0 = c.x0;
-            xokm = 0;
-#pragma unroll
-            for (int i = 0; i < NR; ++i)
-                xokm |= ((unsigned)(i < NR - 1 || tp < 128) & (unsigned)((unsigned)(c.x0 - 1 + (rp[i] & 255)) < (unsigned)W)) << i;
-        }
-    };
-    auto xform = [&](u32x4 raw, bool ok) __attribute__((always_inline)) {
-        if constexpr (!XF) return raw;
-        u32x4 u = act8_bf16(raw, sc0, sc1, sh0, sh1, a_floor16);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) u[e] = ok ? u[e] : 0u;
-        return u;
-    };
-    auto load_consts = [&](const Cur& c) __attribute__((always_inline)) {
-        if constexpr (XF) {
-            if (S.scale) {
-                const long go = S.gN > 0 ? (long)(c.img / S.gN) * S.gstride : 0;
-                const float* scp = S.scale + go + 8 * (tp & 7);
-                const float* shp = S.shift + go + 8 * (tp & 7);
-                sc0 = *(const f32x4*)scp; sc1 = *(const f32x4*)(scp + 4);
-                sh0 = *(const f32x4*)shp; sh1 = *(const f32x4*)(shp + 4);
-            }
-        }
-    };
     // the parked rows of a half -> global (16 px x 64 B per store instruction) + statistics of the stored values
-    // byte offset of piece tt of half HF of cursor c's step in the output (and in y: same layout); bit 31 set outside the image
-    auto piece_off = [&](int HF, int tt, const Cur& c, bool live) __attribute__((always_inline)) {
-        const int i = 2 * HF + (tt >> 1), px = 16 * (tt & 1) + pp;
-        const int y = c.ybeg + 8 * (c.k - 1) + 4 * wm + i;
-        const int ylim = min(c.ybeg + 8 * c.S, H);        // the item's rows (uniform plan: seg = 8 S but for an image's last segment)
-        const bool inimg = live & (y < ylim) & (c.x0 + px < W);
-        return inimg ? (unsigned)(st_lane + (tt & 1) * 2048 + __builtin_amdgcn_readfirstlane(c.img * out_bytes + (y * W + c.x0) * 128)) : 0x80000000u;
-    };
     auto epi_B = [&](int HF, int tt, const Cur& c, bool live, int set = 0) __attribute__((always_inline)) {
         const int i = 2 * HF + (tt >> 1), px = 16 * (tt & 1) + pp;
-        const int y = c.ybeg + 8 * (c.k - 1) + 4 * wm + i;
-        const int ylim = min(c.ybeg + 8 * c.S, H);        // the item's rows (uniform plan: seg = 8 S but for an image's last segment)
         u32x4 u = *(const u32x4*)(Ew + (i * 32 + px) * EPITCH + o * 16);
-        const bool inimg = live & (y < ylim) & (c.x0 + px < W);
+        bool inimg;
         // (row offset in the vector offset, soffset 0: see the four-wave kernel's epi_B)
-        const unsigned voff = inimg ? (unsigned)(st_lane + (tt & 1) * 2048 + __builtin_amdgcn_readfirstlane(c.img * out_bytes + (y * W + c.x0) * 128)) : 0x80000000u;
+        const unsigned voff = piece_off(pl, HF, tt, c, live, inimg);
         __builtin_amdgcn_raw_buffer_store_b128(u, ro, voff, 0, 0);
         if constexpr (BNS) {         // (the y piece was fetched from the same offset one step ago: zeros outside the image, like u below)
 #pragma unroll
@@ -1029,43 +881,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64cp_kernel(const IgemmArgs 
                 s2[e] = fma_scalar(dz, yf, s2[e]);
             }
         }
-        if constexpr (STAT) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) u[e] = inimg ? u[e] : 0u;
-            const bf16x8 v = __builtin_bit_cast(bf16x8, u);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float f = (float)v[e];
-                s1[e] = add_scalar(s1[e], f);
-                s2[e] = fma_scalar(f, f, s2[e]);
-            }
-        }
+        if constexpr (STAT) stat_add8(s1, s2, u, inimg);
     };
     auto stat_flush = [&](const Cur& c) __attribute__((always_inline)) {
-        if constexpr (STAT || BNS) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-#pragma unroll
-                for (int d = 4; d < 64; d <<= 1) {
-                    s1[e] += __shfl_xor(s1[e], d);
-                    s2[e] += __shfl_xor(s2[e], d);
-                }
-            }
-            if (lane < 4) {
-                float* row = a.stat + ((long)(c.item * 2 + wm) * 2) * 64 + 32 * wn + 8 * lane;
-                *(f32x4*)row = (f32x4){s1[0], s1[1], s1[2], s1[3]};
-                *(f32x4*)(row + 4) = (f32x4){s1[4], s1[5], s1[6], s1[7]};
-                *(f32x4*)(row + 64) = (f32x4){s2[0], s2[1], s2[2], s2[3]};
-                *(f32x4*)(row + 68) = (f32x4){s2[4], s2[5], s2[6], s2[7]};
-                if (flat && c.ybeg == 0 && c.S == p.steps) {        // a strip nobody cut: its second slot's rows are zeros, written here
-                    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-                    float* row1 = row + 2 * 2 * 64;
-                    *(f32x4*)row1 = z; *(f32x4*)(row1 + 4) = z; *(f32x4*)(row1 + 64) = z; *(f32x4*)(row1 + 68) = z;
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
-        }
+        if constexpr (STAT || BNS) stat_flush8(s1, s2, a.stat, c.item, wm, wn, lane, flat && c.ybeg == 0 && c.S == p.steps);
     };
 
     auto iteration = [&](auto m_c) __attribute__((always_inline)) {
@@ -1075,17 +894,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64cp_kernel(const IgemmArgs 
         // iteration.  Loaded at the end of the previous iteration (as the four-wave kernel does) they are loop-carried registers,
         // and the copies hipcc places at the loop's back edge wait vmcnt(0) -- for the row fetches just issued: ~2000 cycles per
         // iteration that no stamp inside the segments showed
-        load_consts(cw);
+        rf.load_consts<XF>(cw);
         bns_consts(cp, 0); bns_consts(cc, 1);
-        char* wdst = ring + bW * BANKB + loff0;
-        char* wd8 = tp < 128 ? wdst + 8 * (32 * PITCH) : smem + wd8_dummy;
-        const Cur cn = advance(cl);
-        xok_update(cl);
-        const int in_soff = __builtin_amdgcn_readfirstlane(cl.img * img_bytes);
-        auto stage = [&](int i) __attribute__((always_inline)) {
-            *(u32x4*)(i < NR - 1 ? wdst + i * (32 * PITCH) : wd8) = xform(stg[i], (okmW >> i) & 1u);
-            stg[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, offL[i], in_soff, 0);
-        };
+        const Cur cn = ws_advance(p, H, it1, cl, flat);
+        rf.xok_update(cl);
+        rf.aim(ring + bW * BANKB, smem, __builtin_amdgcn_readfirstlane(cl.img * img_bytes));
+        bool in_;              // (piece_off's second result, not needed for the y fetches)
         // ---- consumers' half 0: the owed stores of the previous step's half 1, then the staging of the next group ----
         if constexpr (DIAG) dt0 = stamp();
 #pragma unroll
@@ -1093,12 +907,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64cp_kernel(const IgemmArgs 
         if (pend && cp.k == cp.S) stat_flush(cp);
         if constexpr (BNS) {         // half 1 of THIS step is stored at the top of the next iteration (its cp = cc, its pend = live)
 #pragma unroll
-            for (int tt = 0; tt < 4; ++tt) ypre[tt] = __builtin_amdgcn_raw_buffer_load_b128(ry, piece_off(1, tt, cc, live), 0, 0);
+            for (int tt = 0; tt < 4; ++tt) ypre[tt] = __builtin_amdgcn_raw_buffer_load_b128(ry, piece_off(pl, 1, tt, cc, live, in_), 0, 0);
         }
 #pragma unroll
-        for (int i = 0; i < NR; ++i) offsets_one(cl, i);
+        for (int i = 0; i < decltype(rf)::NR; ++i) rf.offsets_one(cl, i);
 #pragma unroll
-        for (int i = 0; i < 5; ++i) stage(i);
+        for (int i = 0; i < 5; ++i) rf.stage<XF>(i);
         if constexpr (DIAG) { dt1 = stamp(); dsum[0] += dt1 - dt0; dt0 = dt1; }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                           // B1: half 0 of this step is parked
@@ -1110,11 +924,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64cp_kernel(const IgemmArgs 
         if constexpr (BNS) {         // half 0 of the NEXT step (its cc = cw) is stored in the next iteration's second half
             const bool live_n = cw.valid && cw.k >= 1;
 #pragma unroll
-            for (int tt = 0; tt < 4; ++tt) ypre[4 + tt] = __builtin_amdgcn_raw_buffer_load_b128(ry, piece_off(0, tt, cw, live_n), 0, 0);
+            for (int tt = 0; tt < 4; ++tt) ypre[4 + tt] = __builtin_amdgcn_raw_buffer_load_b128(ry, piece_off(pl, 0, tt, cw, live_n, in_), 0, 0);
         }
 #pragma unroll
-        for (int i = 5; i < NR; ++i) stage(i);
-        okmW = okmL;
+        for (int i = 5; i < decltype(rf)::NR; ++i) rf.stage<XF>(i);
+        rf.okmW = rf.okmL;
         if constexpr (DIAG) { dt1 = stamp(); dsum[2] += dt1 - dt0; dt0 = dt1; }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                           // B2: half 1 parked; the ring bank written above is complete
@@ -1123,58 +937,28 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64cp_kernel(const IgemmArgs 
         cp = cc; pend = live;
         cc = cw; cw = cl; cl = cn;
     };
-    while (true) {
-        if (!(cl.valid | cw.valid | cc.valid | (int)pend)) break;
-        iteration(ic<0>{});
-        if (!(cl.valid | cw.valid | cc.valid | (int)pend)) break;
-        iteration(ic<1>{});
-        if (!(cl.valid | cw.valid | cc.valid | (int)pend)) break;
-        iteration(ic<2>{});
-    }
-    if constexpr (DIAG) {
-        if (lane == 0 && p.dbg) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) p.dbg[((long)blockIdx.x * 8 + wave8) * 8 + k] = dsum[k];
-        }
-    }
+    ring_loop([&]() { return (cl.valid | cw.valid | cc.valid | (int)pend) != 0; }, iteration);
+    if constexpr (DIAG) diag_dump(p.dbg, dsum, lane, (long)blockIdx.x * 8 + wave8);
 }
 
 // which build serves a launch (conv3x3_ws64_launch_bf16): the consumer / producer waves unless a debug flag forces another
 static bool ws_cp_build() { return (g_debug_flags & 32) ? true : (g_debug_flags & (16 | 4 | 2)) ? false : true; }
 
-// segments per strip: whole waves of blocks over the 256 CUs, few bubbles (one staging-only iteration per item) -- or, where that
-// leaves a round of items half empty, the flat plan (WsPlan): equal step counts per block
-WsPlan ws_plan(const IgemmArgs& a) {
-    WsPlan p;
-    p.sx = cdiv(a.Wb, TW);
-    const int steps = cdiv(a.Hb, 8);
-    double best = 1e30;
-    p.sy = 1;
-    for (int sy = 1; sy <= steps; ++sy) {
-        const int per = cdiv(steps, sy);
-        if (cdiv(steps, per) != sy) continue;                 // (no empty segments)
-        const long items = (long)a.N * p.sx * sy;
-        const long ipb = (items + 255) / 256;
-        const double cost = (double)ipb * (per + 1.5);
-        if (cost < best - 1e-9) { best = cost; p.sy = sy; }
-    }
-    p.seg = cdiv(steps, p.sy) * 8;
-    p.items = a.N * p.sx * p.sy;
-    p.ipb = (p.items + 255) / 256;
-    p.L = 0; p.steps = steps;
-    p.dbg = nullptr;
-    // the flat plan: L steps per block, its range touching at most cdiv(L - 1, steps) + 1 strips (ustrun_debug_flags2 bit 2 keeps
-    // the uniform plan: A/B runs)
-    const long total = (long)a.N * p.sx * steps;
-    const int L = (int)((total + 255) / 256);
-    if (ws_cp_build() && !(g_debug_flags2 & 4) && L >= steps && total < (1L << 30)) {
-        const double cost = L + 1.5 * (cdiv(L - 1, steps) + 1);
-        if (cost < 0.97 * best) p.L = L;
-    }
-    return p;
+static WsPlan ws_plan_of(const IgemmArgs& a) {          // (ustrun_debug_flags2 bit 2 keeps the uniform plan: A/B runs)
+    return ws_plan(a.N, a.Hb, a.Wb, ws_cp_build(), (g_debug_flags2 & 4) != 0);
 }
-static int ws_grid(const IgemmArgs& a, const WsPlan& p) {
-    return p.L > 0 ? (int)cdiv((long)a.N * p.sx * p.steps, (long)p.L) : cdiv(p.items, p.ipb);
+
+// One launch: b = the four kernels of a build, [2 XF + STAT]
+using WsKernel = void (*)(const IgemmArgs, const WsPlan);
+static int ws_launch(const WsKernel (&b)[4], bool xf, bool stat, int threads, int lds, const char* name, int variant, int grid, const IgemmArgs& a,
+                     const WsPlan& p, hipStream_t st) {
+    const void* fn = (const void*)b[2 * (int)xf + (int)stat];
+    set_last_variant(variant);
+    USTRUN_TRY(ensure_dynamic_lds(fn, lds, name));
+    void* args[] = {(void*)&a, (void*)&p};
+    (void)hipLaunchKernel(fn, dim3(grid), dim3(threads), args, lds, st);
+    USTRUN_LAUNCH_CHECK(name);
+    return 0;
 }
 
 }  // namespace
@@ -1188,12 +972,12 @@ bool ws64_supported(const IgemmArgs& a) {
     if (s.sC != 1 || s.esz != 2 || s.pool || s.off_y || s.off_x || s.H != a.Hb || s.W != a.Wb || s.sW != 64) return false;
     if (a.Ho != a.Hb || a.Wo != a.Wb || a.Wb < 32 || a.Hb < 16) return false;
     if ((long)a.N * s.sN * 2 >= 0x7fffffffL || (long)a.N * a.Hb * a.Wb * 128 >= 0x7fffffffL) return false;     // one buffer descriptor each
-    const WsPlan p = ws_plan(a);
+    const WsPlan p = ws_plan_of(a);
     return p.items >= 192;              // smaller problems (the batch-1 forward): the tiled kernel fills the chip better
 }
 
-// two rows (one per consumer-wave pair) per item; flat plan: per slot, two slots per strip
-int ws64_stat_rows(const IgemmArgs& a) { const WsPlan p = ws_plan(a); return p.L > 0 ? a.N * p.sx * 4 : p.items * 2; }
+int ws64_stat_rows(const IgemmArgs& a) { return ws_stat_rows(a.N, ws_plan_of(a)); }
+
 
 // can the streaming kernel's input gradient also form the BatchNorm-backward sums of the layer whose da it writes?
 bool ws64_bnsum_supported(const IgemmArgs& a) {
@@ -1204,17 +988,12 @@ bool ws64_bnsum_supported(const IgemmArgs& a) {
 }
 
 int conv3x3_ws64_launch_bf16(const IgemmArgs& a, hipStream_t st) {
-    WsPlan p = ws_plan(a);
-    const int grid = ws_grid(a, p);
+    WsPlan p = ws_plan_of(a);
+    const int grid = ws_grid(a.N, p);
     USTRUN_TRY(debug_buffer_for(grid, "conv3x3_ws64_bf16", &p.dbg));     // set: the DIAG build runs and writes [block][wave][8] u64 there
-    bool xf = false;
-    set_last_variant(0x57530000 | ((a.src[0].scale != nullptr || a.src[0].relu != 0) ? 1 : 0));     // 'WS' | XF
-    xf |= a.src[0].scale != nullptr || a.src[0].relu != 0;
-    USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64_kernel<true, true>, LDSB, "conv3x3_ws64_bf16"));
-    USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64_kernel<true, false>, LDSB, "conv3x3_ws64_bf16"));
-    USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64_kernel<false, true>, LDSB, "conv3x3_ws64_bf16"));
-    USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64_kernel<false, false>, LDSB, "conv3x3_ws64_bf16"));
-    const bool stat = a.stat != nullptr;
+    const bool xf = a.src[0].scale != nullptr || a.src[0].relu != 0, stat = a.stat != nullptr, diag = p.dbg != nullptr;
+    const int WS = 0x57530000 | (xf ? 1 : 0);                               // 'WS' | XF
+    set_last_variant(WS);
     // Which build (measured in one process, N = 64 images of 256^2, profiles/r03_ab_ws64_8waves.log): the eight-wave kernel wins on the
     // plain-source launches (input gradients: 0.320 vs 0.333 ms) and loses where the loader transforms and statistics are taken
     // (forward: 0.394 vs 0.339 ms) -- its per-wave address / cursor / wait instructions double per SIMD while a 16x16x32 MFMA
@@ -1224,71 +1003,41 @@ int conv3x3_ws64_launch_bf16(const IgemmArgs& a, hipStream_t st) {
     const bool cpw = ws_cp_build();
     USTRUN_CHECK(cpw || p.L == 0, "conv3x3_ws64: the flat plan belongs to the consumer / producer build");
     const int flatbit = p.L > 0 ? 0x800 : 0;          // variant code: | 0x800 = flat plan
-    if (cpw && p.dbg) {          // stamped build: [block][wave 0..7][8] u64 (0/2: work of the two segments, 1/3: waits at B1 / B2, 5: iterations)
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64cp_kernel<true, true, true>, LDSBCP, "conv3x3_ws64cp_bf16 (diag)"));
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64cp_kernel<false, false, true>, LDSBCP, "conv3x3_ws64cp_bf16 (diag)"));
-        if (xf) hipLaunchKernelGGL((conv3x3_ws64cp_kernel<true, true, true>), dim3(grid), dim3(512), LDSBCP, st, a, p);
-        else hipLaunchKernelGGL((conv3x3_ws64cp_kernel<false, false, true>), dim3(grid), dim3(512), LDSBCP, st, a, p);
-        USTRUN_LAUNCH_CHECK("conv3x3_ws64cp_bf16 (diag)");
-        return 0;
+    // the stamped (DIAG) builds exist with the transform and the statistics, or with neither; they leave the variant code at 'WS' | XF
+    if (cpw && diag) {           // [block][wave 0..7][8] u64 (0/2: work of the two segments, 1/3: waits at B1 / B2, 5: iterations)
+        static const WsKernel k[4] = {conv3x3_ws64cp_kernel<false, false, true>, conv3x3_ws64cp_kernel<false, false, true>,
+                                      conv3x3_ws64cp_kernel<true, true, true>, conv3x3_ws64cp_kernel<true, true, true>};
+        return ws_launch(k, xf, stat, 512, LDSBCP, "conv3x3_ws64cp_bf16 (diag)", WS, grid, a, p, st);
     }
     if (a.bny) {                  // input gradient + BatchNorm-backward sums: the consumer / producer build only (ws64_bnsum_supported)
-        USTRUN_CHECK(cpw && !p.dbg && !xf && a.stat && a.bnsc && a.bnsh, "conv3x3_ws64: BatchNorm-backward sums need the plain consumer / producer build");
-        set_last_variant(0x57530000 | 0x200 | 0x400 | flatbit);                 // 'WS' | consumer/producer | sums
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64cp_kernel<false, false, false, true>, LDSBCP, "conv3x3_ws64cp_bf16"));
-        hipLaunchKernelGGL((conv3x3_ws64cp_kernel<false, false, false, true>), dim3(grid), dim3(512), LDSBCP, st, a, p);
-        USTRUN_LAUNCH_CHECK("conv3x3_ws64cp_bf16");
-        return 0;
+        USTRUN_CHECK(cpw && !diag && !xf && a.stat && a.bnsc && a.bnsh, "conv3x3_ws64: BatchNorm-backward sums need the plain consumer / producer build");
+        static const WsKernel k[4] = {conv3x3_ws64cp_kernel<false, false, false, true>, conv3x3_ws64cp_kernel<false, false, false, true>,
+                                      conv3x3_ws64cp_kernel<false, false, false, true>, conv3x3_ws64cp_kernel<false, false, false, true>};
+        return ws_launch(k, xf, stat, 512, LDSBCP, "conv3x3_ws64cp_bf16", 0x57530000 | 0x200 | 0x400 | flatbit, grid, a, p, st);     // 'WS' | consumer/producer | sums
     }
-    if (cpw && !p.dbg) {
-        set_last_variant(0x57530000 | 0x200 | flatbit | (xf ? 1 : 0));       // 'WS' | consumer/producer | XF
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64cp_kernel<true, true>, LDSBCP, "conv3x3_ws64cp_bf16"));
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64cp_kernel<true, false>, LDSBCP, "conv3x3_ws64cp_bf16"));
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64cp_kernel<false, true>, LDSBCP, "conv3x3_ws64cp_bf16"));
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64cp_kernel<false, false>, LDSBCP, "conv3x3_ws64cp_bf16"));
-        const bool stat_ = a.stat != nullptr;
-        if (xf && stat_) hipLaunchKernelGGL((conv3x3_ws64cp_kernel<true, true>), dim3(grid), dim3(512), LDSBCP, st, a, p);
-        else if (xf) hipLaunchKernelGGL((conv3x3_ws64cp_kernel<true, false>), dim3(grid), dim3(512), LDSBCP, st, a, p);
-        else if (stat_) hipLaunchKernelGGL((conv3x3_ws64cp_kernel<false, true>), dim3(grid), dim3(512), LDSBCP, st, a, p);
-        else hipLaunchKernelGGL((conv3x3_ws64cp_kernel<false, false>), dim3(grid), dim3(512), LDSBCP, st, a, p);
-        USTRUN_LAUNCH_CHECK("conv3x3_ws64cp_bf16");
-        return 0;
+    if (cpw) {
+        static const WsKernel k[4] = {conv3x3_ws64cp_kernel<false, false>, conv3x3_ws64cp_kernel<false, true>, conv3x3_ws64cp_kernel<true, false>,
+                                      conv3x3_ws64cp_kernel<true, true>};
+        return ws_launch(k, xf, stat, 512, LDSBCP, "conv3x3_ws64cp_bf16", WS | 0x200 | flatbit, grid, a, p, st);         // 'WS' | consumer/producer | XF
     }
-    if (eight && p.dbg) {                        // stamped build of the eight-wave kernel: [block][wave 0..7][8] u64
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64x8_kernel<true, true, true>, LDSB8, "conv3x3_ws64x8_bf16 (diag)"));
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64x8_kernel<false, false, true>, LDSB8, "conv3x3_ws64x8_bf16 (diag)"));
-        if (xf) hipLaunchKernelGGL((conv3x3_ws64x8_kernel<true, true, true>), dim3(grid), dim3(512), LDSB8, st, a, p);
-        else hipLaunchKernelGGL((conv3x3_ws64x8_kernel<false, false, true>), dim3(grid), dim3(512), LDSB8, st, a, p);
-        USTRUN_LAUNCH_CHECK("conv3x3_ws64x8_bf16 (diag)");
-        return 0;
+    if (eight && diag) {                         // stamped build of the eight-wave kernel: [block][wave 0..7][8] u64
+        static const WsKernel k[4] = {conv3x3_ws64x8_kernel<false, false, true>, conv3x3_ws64x8_kernel<false, false, true>,
+                                      conv3x3_ws64x8_kernel<true, true, true>, conv3x3_ws64x8_kernel<true, true, true>};
+        return ws_launch(k, xf, stat, 512, LDSB8, "conv3x3_ws64x8_bf16 (diag)", WS, grid, a, p, st);
     }
     if (eight) {                                 // round 3: eight waves, two per SIMD
-        set_last_variant(0x57530000 | 0x100 | (xf ? 1 : 0));       // 'WS' | 8 waves | XF
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64x8_kernel<true, true>, LDSB8, "conv3x3_ws64x8_bf16"));
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64x8_kernel<true, false>, LDSB8, "conv3x3_ws64x8_bf16"));
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64x8_kernel<false, true>, LDSB8, "conv3x3_ws64x8_bf16"));
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64x8_kernel<false, false>, LDSB8, "conv3x3_ws64x8_bf16"));
-        if (xf && stat) hipLaunchKernelGGL((conv3x3_ws64x8_kernel<true, true>), dim3(grid), dim3(512), LDSB8, st, a, p);
-        else if (xf) hipLaunchKernelGGL((conv3x3_ws64x8_kernel<true, false>), dim3(grid), dim3(512), LDSB8, st, a, p);
-        else if (stat) hipLaunchKernelGGL((conv3x3_ws64x8_kernel<false, true>), dim3(grid), dim3(512), LDSB8, st, a, p);
-        else hipLaunchKernelGGL((conv3x3_ws64x8_kernel<false, false>), dim3(grid), dim3(512), LDSB8, st, a, p);
-        USTRUN_LAUNCH_CHECK("conv3x3_ws64x8_bf16");
-        return 0;
+        static const WsKernel k[4] = {conv3x3_ws64x8_kernel<false, false>, conv3x3_ws64x8_kernel<false, true>, conv3x3_ws64x8_kernel<true, false>,
+                                      conv3x3_ws64x8_kernel<true, true>};
+        return ws_launch(k, xf, stat, 512, LDSB8, "conv3x3_ws64x8_bf16", WS | 0x100, grid, a, p, st);                    // 'WS' | 8 waves | XF
     }
-    if (p.dbg) {
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64_kernel<true, true, true>, LDSB, "conv3x3_ws64_bf16 (diag)"));
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_ws64_kernel<false, false, true>, LDSB, "conv3x3_ws64_bf16 (diag)"));
-        if (xf) hipLaunchKernelGGL((conv3x3_ws64_kernel<true, true, true>), dim3(grid), dim3(256), LDSB, st, a, p);
-        else hipLaunchKernelGGL((conv3x3_ws64_kernel<false, false, true>), dim3(grid), dim3(256), LDSB, st, a, p);
-        USTRUN_LAUNCH_CHECK("conv3x3_ws64_bf16 (diag)");
-        return 0;
+    if (diag) {
+        static const WsKernel k[4] = {conv3x3_ws64_kernel<false, false, true>, conv3x3_ws64_kernel<false, false, true>,
+                                      conv3x3_ws64_kernel<true, true, true>, conv3x3_ws64_kernel<true, true, true>};
+        return ws_launch(k, xf, stat, 256, LDSB, "conv3x3_ws64_bf16 (diag)", WS, grid, a, p, st);
     }
-    if (xf && stat) hipLaunchKernelGGL((conv3x3_ws64_kernel<true, true>), dim3(grid), dim3(256), LDSB, st, a, p);
-    else if (xf) hipLaunchKernelGGL((conv3x3_ws64_kernel<true, false>), dim3(grid), dim3(256), LDSB, st, a, p);
-    else if (stat) hipLaunchKernelGGL((conv3x3_ws64_kernel<false, true>), dim3(grid), dim3(256), LDSB, st, a, p);
-    else hipLaunchKernelGGL((conv3x3_ws64_kernel<false, false>), dim3(grid), dim3(256), LDSB, st, a, p);
-    USTRUN_LAUNCH_CHECK("conv3x3_ws64_bf16");
-    return 0;
+    static const WsKernel k[4] = {conv3x3_ws64_kernel<false, false>, conv3x3_ws64_kernel<false, true>, conv3x3_ws64_kernel<true, false>,
+                                  conv3x3_ws64_kernel<true, true>};
+    return ws_launch(k, xf, stat, 256, LDSB, "conv3x3_ws64_bf16", WS, grid, a, p, st);
 }
 
 }  // namespace ustrun
