@@ -663,6 +663,31 @@ int ustrun_aug_strong(const uint8_t* img, const int32_t* params, int32_t stride,
 int ustrun_aug_finish(const uint8_t* weak, const uint8_t* strong, const uint8_t* lab, int32_t B, int32_t H, int32_t W,
                       int32_t C, int32_t Cl, float* xw, float* xs, float* y, ustrun_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Segmentation overlays of `test.py --save_img` (csrc/render.hip).  The reference
+ * draws them per image on the host in numpy / cv2 (utils/util.py:299-390, called at test.py:110-113);
+ * here a batch is rendered on the device and three bytes per pixel reach the host.
+ *   img [N][C][H][W] f32 (C = 1 or 3; one channel is repeated to three), out [N][H][W][3] uint8 RGB.
+ *   pred / gt, by `kind`: 0 = f32 planes [N][P][H][W]; 1 = int64 labels [N][H][W], part i = label i + 1.
+ *   H, W <= 8192, N <= 65535.
+ * ---------------------------------------------------------------------------------------- */
+/* range[n] = {min, max} of image n over all its channels (img.min() / img.max() of util.py:357,378-380).       */
+int ustrun_render_range(const float* img, int32_t N, int32_t C, int32_t H, int32_t W, float* range,
+                        ustrun_stream_t stream);
+/* draw_mask_and_save (util.py:367-390): v = (img + 1) * 127.5 where the image's min < -0.5, else img * 255 where
+ * its max < 1.5, else img (f32, each step rounded); a pixel of part i (kind 0: value == 1) takes colour_i =
+ * {red, green, blue, yellow, magenta}[i] and factor 0.5, the lowest i winning; out = trunc((v + colour) * factor)
+ * in double, clamped to 0..255 (the reference's cast is undefined outside that range).  P <= 5.                   */
+int ustrun_render_mask(const float* img, const float* range, const void* pred, int32_t pred_kind, int32_t N, int32_t C,
+                       int32_t P, int32_t H, int32_t W, uint8_t* out, ustrun_stream_t stream);
+/* draw_contour_and_save (util.py:299-365): v = (img - min) / (max - min) * 255 (f32, each step rounded; 0 where
+ * max == min, the reference has NaN there); for i = 0..P-1 the contour of pred part i in {green, blue, yellow,
+ * magenta}[i], then that of gt part i in red, the last one drawn winning.  A contour pixel is a background pixel
+ * (kind 0: value > 0 is foreground) with a foreground pixel among its 8 neighbours inside the image (cv2.dilate,
+ * 3 x 3, minus the map).  out = v rounded half to even and clamped to 0..255 (cv2's saturating cast).  P <= 4.   */
+int ustrun_render_contour(const float* img, const float* range, const void* pred, const void* gt, int32_t kind,
+                          int32_t N, int32_t C, int32_t P, int32_t H, int32_t W, uint8_t* out, ustrun_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,10 +2,13 @@
 """test.py -- MI355X build of the reference's evaluation driver (test.py:19-250).
 
 Same command line (flag names and defaults of test.py:19-32; `--dataset` also accepts BUSI, which the reference
-trains but does not list here); additive flags: --synthetic, --data_root, --test_batches, --backend_dtype, --seed, --surface_metrics.  Loads
+trains but does not list here); additive flags: --synthetic, --data_root, --test_batches, --backend_dtype, --seed, --surface_metrics,
+--save_dir, --save_img_mode.  Loads
 `../model/<dataset>/<save_name>/unet_avg_dice_best_model.pth` (a plain state_dict with the reference's keys, test.py:241)
 and prints the per-domain and mean Dice of ustrun.evaluate.validate; `--surface_metrics 1` adds the reference's
-dc / jc / hd / asd lines (test.py:117-136,160-176), computed on the device instead of with medpy.  Batches come from the
+dc / jc / hd / asd lines (test.py:117-136,160-176), computed on the device instead of with medpy.  `--save_img` writes the
+reference's one picture per test image (test.py:110-113) under ./img/save (or --save_dir), rendered on the device
+(ustrun/render.py); `--save_img_mode contour` draws the library's other view, prediction against ground truth.  Batches come from the
 seeded synthetic generator, or with --synthetic 0 from the test splits under --data_root (ustrun/datasets.py).
 """
 import argparse
@@ -38,6 +41,9 @@ parser.add_argument('--load_path', type=str, default='', help='state_dict file (
 parser.add_argument('--backbone', default='resnet101', choices=['resnet50', 'resnet101'], help='--model deeplabv2')
 parser.add_argument('--surface_metrics', type=int, default=0, choices=[0, 1], help='1: also dc / jc / hd95 / asd per part')
 parser.add_argument('--image_size', type=int, default=0, help='patch extent override (0: the dataset default)')
+parser.add_argument('--save_dir', type=str, default='./img/save', help='--save_img: where the pictures go (test.py:113)')
+parser.add_argument('--save_img_mode', default='mask', choices=['mask', 'contour'],
+                    help='--save_img: draw_mask_and_save (the reference\'s) or draw_contour_and_save')
 
 DOMAINS = {"fundus": 4, "prostate": 6, "MNMS": 4, "BUSI": 1}     # test.py:209-223
 
@@ -59,8 +65,6 @@ def main(args):
     args.domain_num = min(args.domain_num, DOMAINS[args.dataset])
     if args.model not in ('unet', 'deeplabv2'):
         raise SystemExit("--model is 'unet' (the reference's path) or 'deeplabv2' (train.py --model deeplabv2 of this build)")
-    if args.save_img:
-        raise SystemExit("--save_img (cv2 contour drawing, util.py:300-360) is outside this build's scope")
     if args.model == 'deeplabv2':
         from networks.deeplabv2 import DeepLabV2
         model = DeepLabV2(args.backbone, K, pretrained=False, dtype=args.backend_dtype).cuda()
@@ -68,7 +72,8 @@ def main(args):
         model = UNet(n_channels=C, n_classes=K, dtype=args.backend_dtype).cuda()
     path = args.load_path or '../model/{}/{}/{}_avg_dice_best_model.pth'.format(args.dataset, args.save_name, args.model)
     model.load_state_dict(torch.load(path, map_location="cuda"))
-    return validate(args.dataset, model, make_loaders(args, C, H), epoch=args.lb_domain, surface_metrics=bool(args.surface_metrics))
+    return validate(args.dataset, model, make_loaders(args, C, H), epoch=args.lb_domain, surface_metrics=bool(args.surface_metrics),
+                    save_dir=args.save_dir if args.save_img else None, save_mode=args.save_img_mode)
 
 
 if __name__ == "__main__":

@@ -154,6 +154,9 @@ SIGNATURES = {
     "ustrun_aug_strong_work_bytes": (i64, [i32, i32, i32, i32]),
     "ustrun_aug_strong": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i64, vp]),
     "ustrun_aug_finish": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, fp, fp, fp, vp]),
+    "ustrun_render_range": (i32, [fp, i32, i32, i32, i32, fp, vp]),
+    "ustrun_render_mask": (i32, [fp, fp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "ustrun_render_contour": (i32, [fp, fp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
 }
 
 _lib = None

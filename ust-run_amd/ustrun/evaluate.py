@@ -10,8 +10,13 @@ optional (`validate(..., surface_metrics=True)`): borders, the exact squared dis
 statistics run on the device (ustrun_surface_metrics) over the same coalesced batch, one more [N, parts, 6] int32 copy reaches the
 host, and utils.metrics.surface_from_records finishes them in float64; they are averaged as the Dice is.  The per-batch
 loss the reference computes is never accumulated there and is not computed here.
+
+`validate(..., save_dir=...)` is the reference's `--save_img` (test.py:110-113): the coalesced batch is rendered once on the
+device (ustrun/render.py), its uint8 [N,H,W,3] block is copied to the host and written as one PNG per image under the
+reference's file names, on a few host threads beside the next batches' forwards (render.PngWriter).  Nothing else changes: the metrics and the logged lines are those of a run without it.
 """
 import logging
+import os
 
 import numpy as np
 import torch
@@ -19,6 +24,7 @@ import torch
 from utils import metrics
 
 from . import functional as F
+from . import render
 from .trainer import DATASETS, decode_labels
 
 PARTS = {"fundus": ["cup", "disc"], "prostate": ["base"], "BUSI": ["base"], "MNMS": ["lv", "myo", "rv"]}
@@ -58,7 +64,8 @@ def batch_dice(dataset, pred, mask):
 
 
 @torch.no_grad()
-def validate(dataset, model, loaders, epoch=0, log=logging.info, coalesce=64, surface_metrics=False):
+def validate(dataset, model, loaders, epoch=0, log=logging.info, coalesce=64, surface_metrics=False, save_dir=None,
+             save_mode="mask"):
     """loaders: one iterable of (image, raw label) batches per domain (any device; moved to the model's).
     Returns (val_dice[parts], per_domain[domain][parts]); leaves the model in train mode, as the reference does.
     surface_metrics=True: returns (val_dice, per_domain, extra) with extra[m] = {"val": [parts], "per_domain": [domain][parts]}
@@ -67,7 +74,16 @@ def validate(dataset, model, loaders, epoch=0, log=logging.info, coalesce=64, su
     In eval mode the samples of a batch do not interact (BatchNorm uses the running statistics), so up to `coalesce`
     images of consecutive loader batches go through ONE forward -- the reference's `test_bs` 1 would otherwise leave the
     deep layers with 8-64 workgroups -- and the Dice is still averaged per loader batch, then per domain, then over the
-    domains, exactly as train.py:318-372 does."""
+    domains, exactly as train.py:318-372 does.
+
+    save_dir: also write one picture per image there, `{domain}_{num}_{avg}.png` as test.py:113 names them (domain from 1, num
+    the running image count from 1 over all domains, avg = round(mean over the parts of the Dice of the image's LOADER batch, 4));
+    save_mode "mask" is the reference's draw_mask_and_save, "contour" its draw_contour_and_save (prediction against ground truth)."""
+    if save_mode not in ("mask", "contour"):
+        raise ValueError("save_mode is 'mask' or 'contour', got %r" % (save_mode,))
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+    writer = render.PngWriter() if save_dir is not None else None
     part = PARTS[dataset]
     dev = next(model.parameters()).device
     model.eval()
@@ -78,6 +94,7 @@ def validate(dataset, model, loaders, epoch=0, log=logging.info, coalesce=64, su
     xper = {m: [] for m in names}
     xdom = {}
     seen = [0, 0]                                           # domain, loader batches flushed in it (for error messages)
+    num = [0]                                               # pictures written so far (test.py:70,112)
 
     def flush(pending, dom):
         if not pending:
@@ -96,9 +113,21 @@ def validate(dataset, model, loaders, epoch=0, log=logging.info, coalesce=64, su
                 raise metrics.EmptyGroundTruth(n, e.part, "domain %d, loader batch %d, " % (seen[0] + 1, seen[1] + b)) from None
         else:
             d = sample_dice(dataset, pred, mask)
+        if save_dir is not None:                            # one render and one uint8 [N,H,W,3] copy per coalesced batch
+            if save_mode == "mask":
+                rgb = render.render_mask(image, pred, parts=len(part))
+            else:
+                rgb = render.render_contour(image, pred, mask, parts=len(part))
+            rgb = rgb.cpu().numpy()
         o = 0
         for b in pending:                                   # the batch's Dice = mean over ITS samples
             n = len(b[0])
+            if save_dir is not None:                        # test.py:108-113
+                dice = [float(sum(d[o:o + n, p]) / n) for p in range(len(part))]
+                avg = round(sum(dice) / len(dice), 4)
+                for j in range(o, o + n):
+                    num[0] += 1
+                    writer.save(rgb[j], os.path.join(save_dir, "%d_%d_%s.png" % (seen[0] + 1, num[0], avg)))
             for p in range(len(part)):
                 dom[p] += float(sum(d[o:o + n, p]) / n)
                 for m, v in zip(names, x if surface_metrics else ()):
@@ -107,31 +136,35 @@ def validate(dataset, model, loaders, epoch=0, log=logging.info, coalesce=64, su
         seen[1] += len(pending)
         return len(pending)
 
-    for i, loader in enumerate(loaders):
-        dom, nb, pending, held = [0.0] * len(part), 0, [], 0
-        seen[0], seen[1] = i, 0
-        for m in names:
-            xdom[m] = [0.0] * len(part)
-        for image, label in loader:
-            image, label = image.to(dev), label.to(dev)
-            if pending and (held + len(image) > coalesce or image.shape[1:] != pending[0][0].shape[1:]):
-                nb += flush(pending, dom)
-                pending, held = [], 0
-            pending.append((image, label))
-            held += len(image)
-        nb += flush(pending, dom)
-        dom = [d / max(nb, 1) for d in dom]
-        per_domain.append(dom)
-        for p in range(len(part)):
-            val[p] += dom[p]
-        for m in names:
-            xdom[m] = [d / max(nb, 1) for d in xdom[m]]
-            xper[m].append(xdom[m])
+    try:
+        for i, loader in enumerate(loaders):
+            dom, nb, pending, held = [0.0] * len(part), 0, [], 0
+            seen[0], seen[1] = i, 0
+            for m in names:
+                xdom[m] = [0.0] * len(part)
+            for image, label in loader:
+                image, label = image.to(dev), label.to(dev)
+                if pending and (held + len(image) > coalesce or image.shape[1:] != pending[0][0].shape[1:]):
+                    nb += flush(pending, dom)
+                    pending, held = [], 0
+                pending.append((image, label))
+                held += len(image)
+            nb += flush(pending, dom)
+            dom = [d / max(nb, 1) for d in dom]
+            per_domain.append(dom)
             for p in range(len(part)):
-                xval[m][p] += xdom[m][p]
-        if log:
-            log("domain%d epoch %d :\n\t%s" % (i + 1, epoch, "".join("val_%s_dice: %f, " % (n, dom[k]) for k, n in enumerate(part)))
-                + _surface_lines(part, xdom))
+                val[p] += dom[p]
+            for m in names:
+                xdom[m] = [d / max(nb, 1) for d in xdom[m]]
+                xper[m].append(xdom[m])
+                for p in range(len(part)):
+                    xval[m][p] += xdom[m][p]
+            if log:
+                log("domain%d epoch %d :\n\t%s" % (i + 1, epoch, "".join("val_%s_dice: %f, " % (n, dom[k]) for k, n in enumerate(part)))
+                    + _surface_lines(part, xdom))
+    finally:
+        if writer is not None:                              # the files are complete when validate returns
+            writer.close()
     model.train()
     val = [v / max(len(loaders), 1) for v in val]
     for m in names:
