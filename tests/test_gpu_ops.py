@@ -314,10 +314,13 @@ def test_conv3x3_f32x3(n, c0, c1, co, h, w, exact):
             lib.ustrun_debug_flags(old)
 
 
-@pytest.mark.parametrize("n,c,h,w", [(2, 3, 16, 32), (1, 1, 19, 37), (3, 3, 40, 33), (4, 3, 136, 96), (8, 3, 256, 256)])
+@pytest.mark.parametrize("n,c,h,w", [(2, 3, 16, 32), (1, 1, 19, 37), (3, 3, 40, 33), (4, 3, 136, 96), (8, 3, 256, 256), (1, 2, 3, 17), (2, 3, 5, 48)])
 def test_conv_first_weight_gradient_f32x3(n, c, h, w):
     """The first convolution's weight gradient under dtype 3 (f32 dY): the streaming kernel with three-term products against
-    torch in float64 -- random data within f32 summation noise (3x torch-f32's own distance), integers exact."""
+    torch in float64 -- random data within f32 summation noise (3x torch-f32's own distance), integers exact.  The two short shapes
+    (heights below the prefetch depth and below 8: the prologue prefetches rows past the segment, one segment per strip, a ragged and an
+    exact strip count, fewer items than a block has waves) have the masks, the row clamp and the idle-wave path live at once.  dw sits
+    between sentinels, nothing is written beyond the published partials bound, and accumulate = 1 adds the same gradient again."""
     l = L()
     lib = l.lib()
     g = torch.Generator().manual_seed(5 * c + w)
@@ -332,11 +335,17 @@ def test_conv_first_weight_gradient_f32x3(n, c, h, w):
         xg, dyg = x.contiguous().cuda(), nhwc(dy)
         src = l.nchw_src(xg.data_ptr(), c, h, w)
         nb = lib.ustrun_wgrad_partials_bytes(9, c, 64, n * h * w)
-        part = torch.empty(nb // 4, device="cuda")
-        dw = torch.empty(64, c, 3, 3, device="cuda")
+        part = torch.full((nb // 4 + 1024,), 5.0, device="cuda")
+        Z = 512
+        buf = torch.full((Z + 64 * c * 9 + Z,), 9.0, device="cuda")
+        dw = buf[Z:Z + 64 * c * 9].view(64, c, 3, 3)
         l.check(lib.ustrun_conv3x3_wgrad(C.byref(src), 1, dyg.data_ptr(), n, h, w, 64, dw.data_ptr(), 0, part.data_ptr(), nb, 3, None))
         tol = 1e-7 if exact else max(3 * rel(g32, g64), 2e-6)
         assert rel(dw.cpu(), g64) < tol, (exact, rel(dw.cpu(), g64), rel(g32, g64))
+        l.check(lib.ustrun_conv3x3_wgrad(C.byref(src), 1, dyg.data_ptr(), n, h, w, 64, dw.data_ptr(), 1, part.data_ptr(), nb, 3, None))
+        assert rel(dw.cpu(), 2 * g64) < tol, (exact, rel(dw.cpu(), 2 * g64))
+        assert bool((buf[:Z] == 9.0).all()) and bool((buf[-Z:] == 9.0).all())
+        assert bool((part[nb // 4:] == 5.0).all()), "slabs beyond the published partials bound"
 
 
 @pytest.mark.parametrize("n,ci,co,h,w", [(2, 128, 64, 5, 7), (3, 256, 128, 12, 10), (1, 64, 64, 3, 50), (2, 256, 128, 32, 32), (2, 1024, 512, 4, 4)])
@@ -444,13 +453,15 @@ def test_conv3x3_bf16_mfma(n, ci, co, h, w, exact):
 @pytest.mark.parametrize("elt", ["bf16", "f16"])
 @pytest.mark.parametrize("flags", [0, 1 << 28])
 @pytest.mark.parametrize("n,c,h,w", [(2, 3, 16, 32), (1, 1, 19, 37), (2, 4, 9, 70), (3, 3, 40, 33), (4, 3, 136, 96), (16, 1, 72, 100),
-                                     (64, 3, 64, 64), (8, 3, 256, 256), (5, 1, 288, 288)])
+                                     (64, 3, 64, 64), (8, 3, 256, 256), (5, 1, 288, 288), (1, 2, 3, 17), (2, 3, 5, 48)])
 def test_conv_first_weight_gradient_exact(n, c, h, w, flags, elt):
     """Weight gradient of the first convolution (NCHW f32 network input, C <= 4 -> 64; autograd of nn.Conv2d at unet_parts.py:16 for
     `inc`): the streaming kernel of round 5 (a wave walks a 16-pixel strip a row a step, dY and the lane's im2col row of x fetched
     four steps ahead through range-checked buffer loads, masks applied at use) and, with ustrun_debug_flags bit 28, the tile kernel
     of rounds 1-4.  Small-integer data is exact: image borders (rows above / below, columns left / right), ragged strips (w % 16),
-    segments that do not divide the height, im2col rows past 9 C and accumulation all show as O(1) errors; dw sits between sentinels."""
+    segments that do not divide the height, im2col rows past 9 C and accumulation all show as O(1) errors; dw sits between sentinels.
+    The two short shapes (3 x 17, 5 x 48) have heights below the prefetch depth and below 8 -- the prologue prefetches rows past the
+    segment, one segment per strip -- and fewer items than a block has waves."""
     l = L()
     lib = l.lib()
     t16, code = (torch.bfloat16, 1) if elt == "bf16" else (torch.float16, 2)

@@ -9,22 +9,38 @@
 //  * weight gradient (bf16 MFMA): dW[(c,kh,kw)][co] = sum_p x[c][p+(kh,kw)-1] * dY[p][co] as a
 //    [32 x pixels] x [pixels x 64] GEMM; the im2col rows are built in LDS from the NCHW patch (three
 //    kw-shifted copies keep the 16-byte fragment reads aligned), dY tiles are read transposed.
+//
+// Shared with other files: conv_first_plan.h (the streaming kernels' strip plans, their item decodes and the one predicate for "the
+// streaming weight gradient may run" -- ops.hip asks it too; pinned on the CPU by tests/host/conv_first_plan_check.hip), tn_gemm.h
+// (the transposing fragment reads), x3_split.h (dtype USTRUN_F32X3's three-term split and its six-MFMA product).
 #include "common.h"
-#include "loader.h"
+#include "conv_first_plan.h"
+#include "tn_gemm.h"
+#include "x3_split.h"
 #include <type_traits>
 
 namespace ustrun {
 namespace {
 
-
-constexpr int FTH = 8, FTW = 16, FHW = FTW + 2, FHP = (FTH + 2) * FHW;   // 10 x 18 patch
+constexpr int FTH = 8, FTW = CF_WG_TW, FHW = FTW + 2, FHP = (FTH + 2) * FHW;   // 10 x 18 patch
 constexpr int CMAX = 4;
 
-// x NCHW [N,C,H,W] (strides given), w = packed forward weights (f32 [9][C][64] or bf16 [9][C/8][64][8]),
-// y NHWC [N,H,W,64], stat [tiles][2][64]
-template <int ESZ>
+// GEMM k index (= im2col row) -> (input channel, tap): k = 9 c + tap
+__device__ __forceinline__ void k_decode(int k, int& c, int& tap) { c = k / 9; tap = k - c * 9; }
+
+// the four waves' statistics partials red[wave][sum | sum of squares][channel] -> statistics row `row`, waves added in fixed order
+__device__ __forceinline__ void sum_waves_store_stat(const float (&red)[4][2][64], float* __restrict__ stat, long row) {
+    __syncthreads();
+    const int tid = threadIdx.x;
+    if (tid < 128) {
+        const int q = tid >> 6, c = tid & 63;
+        stat[(row * 2 + q) * 64 + c] = red[0][q][c] + red[1][q][c] + red[2][q][c] + red[3][q][c];
+    }
+}
+
+// x NCHW [N,C,H,W] (strides given), w = packed forward weights f32 [9][C][64], y NHWC [N,H,W,64], stat [tiles][2][64]
 __global__ __launch_bounds__(256) void conv_first_fwd_kernel(const float* __restrict__ x, long sN, long sC, long sH, long sW,
-                                                            int C, int H, int W, const void* __restrict__ w, int wbf16,
+                                                            int C, int H, int W, const float* __restrict__ w,
                                                             float* __restrict__ y, float* __restrict__ stat,
                                                             int tiles_x, int tiles_y) {
     __shared__ float patch[CMAX][FHP];
@@ -41,9 +57,10 @@ __global__ __launch_bounds__(256) void conv_first_fwd_kernel(const float* __rest
         patch[c][hp] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? x[img * sN + c * sC + iy * sH + ix * sW] : 0.f;
     }
     for (int t = tid; t < C * 9 * 64; t += 256) {                    // packed forward weights -> [c*9+tap][co]
-        const int co = t & 63, k = t >> 6, c = k / 9, tap = k - c * 9;
-        wl[k][co] = wbf16 ? (float)((const elt_t*)w)[(((long)tap * ((C + 7) / 8) + c / 8) * 64 + co) * 8 + (c & 7)]
-                          : ((const float*)w)[((long)tap * C + c) * 64 + co];
+        const int co = t & 63, k = t >> 6;
+        int c, tap;
+        k_decode(k, c, tap);
+        wl[k][co] = w[((long)tap * C + c) * 64 + co];
     }
     __syncthreads();
     float s1[16], s2[16];
@@ -71,9 +88,7 @@ __global__ __launch_bounds__(256) void conv_first_fwd_kernel(const float* __rest
         if (oy < H && ox < W) {
             const long o = (((long)img * H + oy) * W + ox) * 64 + wave * 16;
 #pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j] = rndt<ESZ>(acc[j]);        // statistics see the stored value
-#pragma unroll
-            for (int q = 0; q < 4; ++q) st4t<ESZ>(y, o + 4 * q, (f32x4){acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]});
+            for (int q = 0; q < 4; ++q) *(f32x4*)(y + o + 4 * q) = (f32x4){acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
 #pragma unroll
             for (int j = 0; j < 16; ++j) { s1[j] += acc[j]; s2[j] += acc[j] * acc[j]; }
         }
@@ -101,7 +116,7 @@ __global__ __launch_bounds__(256) void conv_first_fwd_kernel(const float* __rest
 // with ds_read_b32 at per-lane constant offsets (k -> (c, tap)) and rounds them to bf16; the weight fragments are
 // block constants kept in registers.  Epilogue as in conv_halo_bf16.hip: per-wave LDS transpose, 16-byte stores,
 // BatchNorm-statistics partials of the stored values (one row per block).
-constexpr int MTH = 8, MTW = 32, MHW = MTW + 2, MHP = (MTH + 2) * MHW;   // 10 x 34 patch
+constexpr int MTH = CF_FWD_TH, MTW = CF_FWD_TW, MHW = MTW + 2, MHP = (MTH + 2) * MHW;   // 10 x 34 patch
 
 template <int KS>
 __global__ __launch_bounds__(256, 4) void conv_first_fwd_mfma_kernel(const float* __restrict__ x, long sN, long sC, long sH, long sW,
@@ -127,7 +142,8 @@ __global__ __launch_bounds__(256, 4) void conv_first_fwd_mfma_kernel(const float
     if (tid < 4) patch[CMAX * MHP + tid] = 0.f;
     for (int t = tid; t < KS * 2 * 64 * 8; t += 256) {       // k = c*9 + tap; packed forward weights are [tap][1][64][8 (c)]
         const int j = t & 7, co = (t >> 3) & 63, k8 = t >> 9, k = k8 * 8 + j;
-        const int c = k / 9, tap = k - c * 9;
+        int c, tap;
+        k_decode(k, c, tap);
         Bw[k8][co][j] = k < K ? w[((long)tap * 64 + co) * 8 + c] : (elt_t)0.f;
     }
     // this lane's K entries: k = 16 ks + 8 lh + j -> patch offset relative to the pixel's (0,0) tap
@@ -136,7 +152,9 @@ __global__ __launch_bounds__(256, 4) void conv_first_fwd_mfma_kernel(const float
     for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int k = 16 * ks + 8 * lh + j, c = k / 9, tap = k - c * 9;
+            const int k = 16 * ks + 8 * lh + j;
+            int c, tap;
+            k_decode(k, c, tap);
             koff[ks][j] = k < K ? c * MHP + (tap / 3) * MHW + tap % 3 : -1;
         }
     __syncthreads();
@@ -204,11 +222,7 @@ __global__ __launch_bounds__(256, 4) void conv_first_fwd_mfma_kernel(const float
             s2[n] += __shfl_xor(s2[n], 32);
             if (lh == 0) { red[wave][0][n * 32 + l31] = s1[n]; red[wave][1][n * 32 + l31] = s2[n]; }
         }
-        __syncthreads();
-        if (tid < 128) {
-            const int q = tid >> 6, c = tid & 63;
-            stat[((long)blockIdx.x * 2 + q) * 64 + c] = red[0][q][c] + red[1][q][c] + red[2][q][c] + red[3][q][c];
-        }
+        sum_waves_store_stat(red, stat, blockIdx.x);
     }
 }
 
@@ -217,9 +231,33 @@ __global__ __launch_bounds__(256, 4) void conv_first_fwd_mfma_kernel(const float
 // waves summed through LDS at the end, one slab per block: slab[(c*9 + t)][co] (rows >= 9C unused)
 constexpr int WRB = 192;     // dY LDS row pitch (64 bf16 + pad: conflict-free transposed reads)
 
-template <int ESZ>
+// a lane's byte offset into a [16 px][WRB] dY tile for tr_frag_rows: pixel row 8 lh + q, columns 16 ((l >> 4) & 1) + 4 (l & 3) ..
+__device__ __forceinline__ int dy_lane_base(int lane) {
+    const int lh = lane >> 5, lrow = 8 * lh + ((lane & 15) >> 2), lcol = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+    return lrow * WRB + lcol * 2;
+}
+
+// Block epilogue of both weight-gradient kernels: sum the four waves' accumulators (fixed order, 0 + 1 + 2 + 3) through LDS and write
+// the block's slab.  accs lives in the dY tiles' memory, hence the barrier in front: every wave is done reading its last tile.
+__device__ __forceinline__ void sum_waves_store_slab(const f32x16 (&acc)[2], float (*accs)[32][64], float* __restrict__ partials) {
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) accs[wave][(r & 3) + 8 * (r >> 2) + 4 * lh][j * 32 + l31] = acc[j][r];
+    __syncthreads();
+    float* slab = partials + (long)blockIdx.x * 32 * 64;
+    for (int e = tid; e < 32 * 64; e += 256) {
+        const int i = e >> 6, co = e & 63;
+        slab[e] = accs[0][i][co] + accs[1][i][co] + accs[2][i][co] + accs[3][i][co];
+    }
+}
+
+// the tile kernel of rounds 1-4 (16-bit dY): the fallback for layouts outside the streaming kernel's range, and ustrun_debug_flags bit 28
 __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const float* __restrict__ x, long sN, long sC, long sH, long sW,
-                                                              int C, int H, int W, const float* __restrict__ dy,
+                                                              int C, int H, int W, const elt_t* __restrict__ dy,
                                                               float* __restrict__ partials, int tiles_x, int tiles_y,
                                                               int ttotal, int tiles_per) {
     // im2col source: xs[c][kw][hy][16] bf16 = patch shifted by kw so that 8 consecutive pixels are 16-B aligned
@@ -228,7 +266,6 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const float* __re
     // 1024 blocks, four per CU, are resident at once; with 60 KB two per CU were, and the kernel ran its grid in two rounds)
     constexpr int DYSB = FTH * FTW * WRB > 4 * 32 * 64 * 4 ? FTH * FTW * WRB : 4 * 32 * 64 * 4;
     __shared__ __attribute__((aligned(16))) char dys[DYSB];
-    float (*accs)[32][64] = (float (*)[32][64])dys;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
     f32x16 acc[2];
@@ -237,16 +274,18 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const float* __re
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
     // this lane's im2col row i = l31 -> (c, kh, kw); rows >= 9C are zero
-    const int irow = l31, ic = irow / 9, it = irow % 9, ikh = it / 3, ikw = it % 3;
-    const bool ivalid = irow < 9 * C;
-    const int lrow = 8 * lh + ((lane & 15) >> 2), lcol = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+    int ic, it;
+    k_decode(l31, ic, it);
+    const int ikh = it / 3, ikw = it % 3;
+    const bool ivalid = l31 < 9 * C;
+    const char* lbase = dys + dy_lane_base(lane);
 
     const int tbeg = blockIdx.x * tiles_per, tend = min(ttotal, tbeg + tiles_per);
     // Register-staged software pipeline: the next tile's dY (16 B per item) and x elements are loaded while the current
     // tile's MFMAs run (the synchronous load -> barrier -> compute loop spent 16 us per 16 KB tile).  The decomposition
     // of this thread's x elements into (channel, kw, patch row, pixel) does not depend on the tile.
     constexpr int XIT = (CMAX * 3 * (FTH + 2) * FTW + 255) / 256;
-    constexpr int DIT = FTH * FTW * (ESZ == 2 ? 8 : 16) / 256;       // 16-byte items: 8 bf16 or 4 f32 channels
+    constexpr int DIT = FTH * FTW * 8 / 256;                         // 16-byte items: 8 channels
     int xdec[XIT];
 #pragma unroll
     for (int i = 0; i < XIT; ++i) {
@@ -270,11 +309,10 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const float* __re
 #pragma unroll
         for (int i = 0; i < DIT; ++i) {
             const int e = tid + 256 * i;
-            const int p = ESZ == 2 ? e >> 3 : e >> 4, g = ESZ == 2 ? e & 7 : e & 15;
+            const int p = e >> 3, g = e & 7;
             const int oy = y0 + (p >> 4), ox = x0 + (p & 15);
             dr[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (oy < H && ox < W)
-                dr[i] = *(const f32x4*)((const char*)dy + ((((long)img * H + oy) * W + ox) * 64 + (ESZ == 2 ? 8 : 4) * g) * ESZ);
+            if (oy < H && ox < W) dr[i] = *(const f32x4*)(dy + (((long)img * H + oy) * W + ox) * 64 + 8 * g);
         }
     };
     if (tbeg < tend) prefetch(tbeg);
@@ -288,13 +326,7 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const float* __re
 #pragma unroll
         for (int i = 0; i < DIT; ++i) {
             const int e = tid + 256 * i;
-            if (ESZ == 2) {
-                *(f32x4*)(dys + (e >> 3) * WRB + (e & 7) * 16) = dr[i];          // 8 bf16, as stored
-            } else {
-                bf16x4 h;
-                h[0] = (elt_t)dr[i][0]; h[1] = (elt_t)dr[i][1]; h[2] = (elt_t)dr[i][2]; h[3] = (elt_t)dr[i][3];
-                *(bf16x4*)(dys + (e >> 4) * WRB + (e & 15) * 8) = h;
-            }
+            *(f32x4*)(dys + (e >> 3) * WRB + (e & 7) * 16) = dr[i];              // 8 elements, as stored
         }
         if (t + 1 < tend) prefetch(t + 1);
         __syncthreads();
@@ -306,28 +338,10 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const float* __re
             for (int q = 0; q < 8; ++q) a[q] = (elt_t)0.f;
             if (ivalid) a = *(const bf16x8*)&xs[ic][ikw][r + ikh][8 * lh];
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const char* base = dys + (r * FTW + lrow) * WRB + (j * 32 + lcol) * 2;
-                const bf16x4 lo = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)base));
-                const bf16x4 hi = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + 4 * WRB)));
-                bf16x8 b;
-                b[0] = lo[0]; b[1] = lo[1]; b[2] = lo[2]; b[3] = lo[3]; b[4] = hi[0]; b[5] = hi[1]; b[6] = hi[2]; b[7] = hi[3];
-                acc[j] = USTRUN_MFMA_32x32x16(a, b, acc[j], 0, 0, 0);
-            }
+            for (int j = 0; j < 2; ++j) acc[j] = USTRUN_MFMA_32x32x16(a, tr_frag_rows<WRB>(lbase + j * 64, r * FTW), acc[j], 0, 0, 0);
         }
     }
-    // sum the four waves (fixed order) and write the block's slab
-    __syncthreads();                              // (every wave is done reading the last dY tile: accs lives in its memory)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) accs[wave][(r & 3) + 8 * (r >> 2) + 4 * lh][j * 32 + l31] = acc[j][r];
-    __syncthreads();
-    float* slab = partials + (long)blockIdx.x * 32 * 64;
-    for (int e = tid; e < 32 * 64; e += 256) {
-        const int i = e >> 6, co = e & 63;
-        slab[e] = accs[0][i][co] + accs[1][i][co] + accs[2][i][co] + accs[3][i][co];
-    }
+    sum_waves_store_slab(acc, (float (*)[32][64])dys, partials);
 }
 
 // ---- weight gradient, streaming form (round 5) -----------------------------------------------------------------------------
@@ -337,13 +351,87 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const float* __re
 // x values of the lane's im2col row (c, kh, kw) -- straight from the NCHW image, which stays in L2 -- are fetched into REGISTERS
 // four steps ahead (the compiler counts those waits itself), the dY piece passes through a wave-private LDS slot for the
 // transposing fragment reads, two MFMAs, next step.  No barrier until the block's four accumulator sets are summed at the end.
-template <int D>
+//
+// One walk, two builds.  `Op` supplies what differs: the dY element, how many 16-byte pieces of a row piece a lane fetches, how a
+// piece lands in the slot, how the x values become the A fragment, and the product.  The pieces' geometry follows from the bytes
+// per pixel: the lane fetches piece 64 i + lane of the row piece = pixel PXS i + lane / PPP, 16-byte channel group lane % PPP.
+template <int PXB_, int PLANES> struct WgPieces {
+    static constexpr int PXB = PXB_;                     // bytes of dY per pixel
+    static constexpr int PPP = PXB / 16;                 // pieces per pixel
+    static constexpr int PXS = 64 / PPP;                 // pixels a wave covers with one piece per lane
+    static constexpr int NP = FTW / PXS;                 // pieces per lane per row
+    static constexpr int SLOT = PLANES * FTW * WRB;      // LDS bytes of one row piece: PLANES planes of [16 px][WRB] 16-bit values
+    static constexpr int LDS = 4 * 2 * SLOT > 4 * 32 * 64 * 4 ? 4 * 2 * SLOT : 4 * 32 * 64 * 4;   // 4 waves x 2 slots, >= the final sum's 32 KB
+    static __device__ __forceinline__ int px(int i, int lane) { return PXS * i + lane / PPP; }
+    static __device__ __forceinline__ int mem_off(int i, int lane) { return px(i, lane) * PXB + (lane % PPP) * 16; }           // in the row piece
+    static __device__ __forceinline__ int lds_off(int i, int lane) { return px(i, lane) * WRB + (lane % PPP) * (2048 / PXB); }  // in a plane
+};
+
+// d & m, one dword at a time (written as one vector operation the 16-bit build takes 152 VGPRs instead of 116: a block per CU less)
+__device__ __forceinline__ u32x4 and4(u32x4 d, unsigned m) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) d[q] &= m;
+    return d;
+}
+
+struct WgOp16 : WgPieces<128, 1> {                       // 16-bit dY (2 KB per step), used as stored: one MFMA per column half
+    typedef elt_t dy_t;
+    typedef bf16x8 afrag;
+    static constexpr const char* NAME = "conv_first_wgrad_stream";
+    static __device__ __forceinline__ void stage(char* sl, int lane, const u32x4 (&d)[NP], const unsigned (&m)[NP]) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) *(u32x4*)(sl + lds_off(i, lane)) = and4(d[i], m[i]);
+    }
+    static __device__ __forceinline__ afrag a_frag(const float (&v)[8]) {
+        afrag a;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) a[q] = (elt_t)v[q];
+        return a;
+    }
+    static __device__ __forceinline__ void multiply(const afrag& a, const char* lbase, f32x16 (&acc)[2]) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[j] = USTRUN_MFMA_32x32x16(a, tr_frag_rows<WRB>(lbase + j * 64, 0), acc[j], 0, 0, 0);
+    }
+};
+
+struct WgOpX3 : WgPieces<256, 3> {                       // dtype USTRUN_F32X3: f32 dY (4 KB per step), both operands split into three
+    typedef float dy_t;                                  // bf16 terms at use (x3.hip's arithmetic: six MFMAs per product, f32-level
+    struct afrag { b16x8 p[3]; };                        // result), three LDS planes per slot
+    static constexpr const char* NAME = "conv_first_wgrad_x3";
+    static __device__ __forceinline__ void stage(char* sl, int lane, const u32x4 (&d)[NP], const unsigned (&m)[NP]) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            char* dst = sl + lds_off(i, lane);
+            split4(__builtin_bit_cast(f32x4, and4(d[i], m[i])), *(u32x2*)dst, *(u32x2*)(dst + FTW * WRB), *(u32x2*)(dst + 2 * FTW * WRB));
+        }
+    }
+    static __device__ __forceinline__ afrag a_frag(const float (&v)[8]) {
+        u32x2 lo[3], hi[3];
+        split4((f32x4){v[0], v[1], v[2], v[3]}, lo[0], lo[1], lo[2]);
+        split4((f32x4){v[4], v[5], v[6], v[7]}, hi[0], hi[1], hi[2]);
+        afrag a;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) a.p[p] = __builtin_bit_cast(b16x8, (u32x4){lo[p][0], lo[p][1], hi[p][0], hi[p][1]});
+        return a;
+    }
+    static __device__ __forceinline__ void multiply(const afrag& a, const char* lbase, f32x16 (&acc)[2]) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            b16x8 b[3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) b[p] = tr_frag_rows<WRB, __bf16>(lbase + p * FTW * WRB + j * 64, 0);
+            acc[j] = mfma6(a.p, b, acc[j]);
+        }
+    }
+};
+
+template <typename Op, int D>
 __global__ __launch_bounds__(256) void conv_first_wgrad_stream_kernel(const float* __restrict__ x, int sN, int sC, int sH, int C,
-                                                                      int H, int W, int xbytes, const elt_t* __restrict__ dy,
+                                                                      int H, int W, int xbytes, const typename Op::dy_t* __restrict__ dy,
                                                                       int dybytes, float* __restrict__ partials, int strips, int segs,
                                                                       int seg_rows, int items) {
-    __shared__ __attribute__((aligned(16))) char dys[4 * 2 * FTW * WRB > 4 * 32 * 64 * 4 ? 4 * 2 * FTW * WRB : 4 * 32 * 64 * 4];
-    float (*accs)[32][64] = (float (*)[32][64])dys;
+    constexpr int NP = Op::NP;
+    extern __shared__ __attribute__((aligned(16))) char dys[];        // Op::LDS bytes: 4 waves x 2 slots, then the final sum
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
@@ -354,11 +442,12 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_stream_kernel(const floa
         for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
     const int item = blockIdx.x * 4 + wave;
     if (item < items) {
-        // (strip fastest: the four waves of a block read four neighbouring 2 KB pieces of the same dY rows)
-        const int sx = item % strips, sg = (item / strips) % segs, img = item / (segs * strips);
-        const int x0 = sx * FTW, r0 = sg * seg_rows, r1 = min(H, r0 + seg_rows);
+        const CfWgradItem w = conv_first_wgrad_item(strips, segs, seg_rows, H, item);
+        const int img = w.img, x0 = w.x0, r0 = w.r0, r1 = w.r1;
         // this lane's im2col row i = l31 -> (c, kh, kw); rows >= 9C are zero
-        const int ic = l31 / 9, it = l31 % 9, ikh = it / 3, ikw = it % 3;
+        int ic, it;
+        k_decode(l31, ic, it);
+        const int ikh = it / 3, ikw = it % 3;
         const bool ivalid = l31 < 9 * C;
         // Both tensors are read through ONE buffer resource each, every load issued unconditionally: an offset outside the tensor
         // (one float in front of the first row, a few behind the last) fails the range check and returns zeros; what must not
@@ -375,13 +464,13 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_stream_kernel(const floa
         unsigned cm[8];                                               // per column: all ones where it lies in the image
 #pragma unroll
         for (int q = 0; q < 8; ++q) cm[q] = (ivalid && (unsigned)(col0 + q) < (unsigned)W) ? 0xffffffffu : 0u;
-        // dY: lane fetches 16-byte piece 64 i + lane of the row's 2 KB: pixel (64 i + lane) >> 3, channel group lane & 7
-        const int dpx0 = lane >> 3, dpx1 = 8 + (lane >> 3), dcg = lane & 7;
-        const unsigned dm0 = x0 + dpx0 < W ? 0xffffffffu : 0u, dm1 = x0 + dpx1 < W ? 0xffffffffu : 0u;
-        const int doff0 = ((img * H * W + x0 + dpx0) * 64 + dcg * 8) * 2, doff1 = doff0 + 8 * 64 * 2;
-        char* slot = dys + wave * (2 * FTW * WRB);
-        const int lrow = 8 * lh + ((lane & 15) >> 2), lcol = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-        u32x4 xr[D][2], dr[D][2];
+        unsigned dm[NP];                                              // per dY piece: all ones where its pixel lies in the image
+#pragma unroll
+        for (int i = 0; i < NP; ++i) dm[i] = x0 + Op::px(i, lane) < W ? 0xffffffffu : 0u;
+        const int doff0 = (img * H * W + x0) * Op::PXB + Op::mem_off(0, lane);
+        char* slot = dys + wave * (2 * Op::SLOT);
+        const int lbase = dy_lane_base(lane);
+        u32x4 xr[D][2], dr[D][NP];
         unsigned rm[D];                                               // per slot: all ones where the lane's x row lies in the image
         auto prefetch = [&](int u, int y) {
             const int yy = y + ikh - 1;
@@ -389,36 +478,28 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_stream_kernel(const floa
             const int xo = xoff0 + yy * sH * 4;
             xr[u][0] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, xo, 0, 0));
             xr[u][1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, xo + 16, 0, 0));
-            const int dofs = min(y, r1 - 1) * W * 128;
-            dr[u][0] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rd, doff0 + dofs, 0, 0));
-            dr[u][1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rd, doff1 + dofs, 0, 0));
+            const int dofs = doff0 + min(y, r1 - 1) * W * Op::PXB;
+#pragma unroll
+            for (int i = 0; i < NP; ++i)
+                dr[u][i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rd, dofs + i * Op::PXS * Op::PXB, 0, 0));
         };
         auto consume = [&](int u, int par, bool live) {
-            char* sl = slot + par * (FTW * WRB);
-            u32x4 d0 = dr[u][0], d1 = dr[u][1];
+            char* sl = slot + par * Op::SLOT;
             const unsigned lm = live ? 0xffffffffu : 0u;              // (wave-uniform: rows past the segment add nothing)
+            unsigned m[NP];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) { d0[q] &= dm0 & lm; d1[q] &= dm1 & lm; }
-            *(u32x4*)(sl + dpx0 * WRB + dcg * 16) = d0;
-            *(u32x4*)(sl + dpx1 * WRB + dcg * 16) = d1;
-            bf16x8 a;
+            for (int i = 0; i < NP; ++i) m[i] = dm[i] & lm;
+            Op::stage(sl, lane, dr[u], m);
             unsigned v[8];
 #pragma unroll
             for (int q = 0; q < 4; ++q) { v[q] = xr[u][0][q]; v[4 + q] = xr[u][1][q]; }
+            float f[8];
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const unsigned t = shl ? (q ? v[q - 1] : 0u) : v[q];
-                a[q] = (elt_t)__builtin_bit_cast(float, t & cm[q] & rm[u]);
+                f[q] = __builtin_bit_cast(float, t & cm[q] & rm[u]);
             }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const char* base = sl + lrow * WRB + (j * 32 + lcol) * 2;
-                const bf16x4 lo = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)base));
-                const bf16x4 hi = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + 4 * WRB)));
-                bf16x8 b;
-                b[0] = lo[0]; b[1] = lo[1]; b[2] = lo[2]; b[3] = lo[3]; b[4] = hi[0]; b[5] = hi[1]; b[6] = hi[2]; b[7] = hi[3];
-                acc[j] = USTRUN_MFMA_32x32x16(a, b, acc[j], 0, 0, 0);
-            }
+            Op::multiply(Op::a_frag(f), sl + lbase, acc);
         };
 #pragma unroll
         for (int u = 0; u < D; ++u) prefetch(u, r0 + u);
@@ -430,149 +511,7 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_stream_kernel(const floa
             }
         }
     }
-    // sum the four waves (fixed order) and write the block's slab
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) accs[wave][(r & 3) + 8 * (r >> 2) + 4 * lh][j * 32 + l31] = acc[j][r];
-    __syncthreads();
-    float* slab = partials + (long)blockIdx.x * 32 * 64;
-    for (int e = tid; e < 32 * 64; e += 256) {
-        const int i = e >> 6, co = e & 63;
-        slab[e] = accs[0][i][co] + accs[1][i][co] + accs[2][i][co] + accs[3][i][co];
-    }
-}
-
-// ---- ... and for dtype USTRUN_F32X3 (f32 dY): the same walk with both operands split into three bf16 terms at use (x3.hip's
-// arithmetic: six MFMAs per product, f32-level result): 4 KB of dY per step, three LDS planes per slot.
-template <int D>
-__global__ __launch_bounds__(256) void conv_first_wgrad_stream_x3_kernel(const float* __restrict__ x, int sN, int sC, int sH, int C,
-                                                                         int H, int W, int xbytes, const float* __restrict__ dy,
-                                                                         int dybytes, float* __restrict__ partials, int strips, int segs,
-                                                                         int seg_rows, int items) {
-    constexpr int SLOT = 3 * FTW * WRB;                                // three planes of [16 px][WRB]
-    extern __shared__ __attribute__((aligned(16))) char dys[];         // 4 waves x 2 slots (>= 4 x 32 x 64 floats for the final sum)
-    float (*accs)[32][64] = (float (*)[32][64])dys;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, lh = lane >> 5;
-    f32x16 acc[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-    auto split1 = [](float v, __bf16& h0, __bf16& h1, __bf16& h2) {
-        h0 = (__bf16)v;
-        const float r1 = v - (float)h0;
-        h1 = (__bf16)r1;
-        h2 = (__bf16)(r1 - (float)h1);
-    };
-    const int item = blockIdx.x * 4 + wave;
-    if (item < items) {
-        const int sx = item % strips, sg = (item / strips) % segs, img = item / (segs * strips);
-        const int x0 = sx * FTW, r0 = sg * seg_rows, r1 = min(H, r0 + seg_rows);
-        const int ic = l31 / 9, it = l31 % 9, ikh = it / 3, ikw = it % 3;
-        const bool ivalid = l31 < 9 * C;
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, xbytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)dy, 0, dybytes, 0x00020000);
-        const int col0 = x0 + 8 * lh + ikw - 1;
-        const bool shl = col0 < 0;                                     // (see the 16-bit kernel: the one lane column that starts in front of its row)
-        const int xoff0 = (img * sN + (ivalid ? ic : 0) * sC + col0 + (shl ? 1 : 0)) * 4;
-        unsigned cm[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) cm[q] = (ivalid && (unsigned)(col0 + q) < (unsigned)W) ? 0xffffffffu : 0u;
-        // dY: lane fetches 16-byte piece 64 i + lane (i < 4) of the row's 4 KB: pixel 4 i + (lane >> 4), 4-channel group lane & 15
-        const int dpx = lane >> 4, dcg = lane & 15;
-        unsigned dm[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dm[i] = x0 + 4 * i + dpx < W ? 0xffffffffu : 0u;
-        const int doff0 = ((img * H * W + x0 + dpx) * 64 + dcg * 4) * 4;
-        char* slot = dys + wave * (2 * SLOT);
-        const int lrow = 8 * lh + ((lane & 15) >> 2), lcol = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-        u32x4 xr[D][2], dr[D][4];
-        unsigned rm[D];
-        auto prefetch = [&](int u, int y) {
-            const int yy = y + ikh - 1;
-            rm[u] = (y < r1 && (unsigned)yy < (unsigned)H) ? 0xffffffffu : 0u;
-            const int xo = xoff0 + yy * sH * 4;
-            xr[u][0] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, xo, 0, 0));
-            xr[u][1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, xo + 16, 0, 0));
-            const int dofs = min(y, r1 - 1) * W * 256;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                dr[u][i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rd, doff0 + dofs + i * 4 * 256, 0, 0));
-        };
-        auto consume = [&](int u, int par, bool live) {
-            char* sl = slot + par * SLOT;
-            const unsigned lm = live ? 0xffffffffu : 0u;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                b16x4 h0, h1, h2;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    __bf16 t0, t1, t2;
-                    split1(__builtin_bit_cast(float, dr[u][i][q] & dm[i] & lm), t0, t1, t2);
-                    h0[q] = t0; h1[q] = t1; h2[q] = t2;
-                }
-                char* dst = sl + (4 * i + dpx) * WRB + dcg * 8;
-                *(u32x2*)dst = __builtin_bit_cast(u32x2, h0);
-                *(u32x2*)(dst + FTW * WRB) = __builtin_bit_cast(u32x2, h1);
-                *(u32x2*)(dst + 2 * FTW * WRB) = __builtin_bit_cast(u32x2, h2);
-            }
-            b16x8 a[3];
-            unsigned v[8];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { v[q] = xr[u][0][q]; v[4 + q] = xr[u][1][q]; }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const unsigned t = shl ? (q ? v[q - 1] : 0u) : v[q];
-                __bf16 t0, t1, t2;
-                split1(__builtin_bit_cast(float, t & cm[q] & rm[u]), t0, t1, t2);
-                a[0][q] = t0; a[1][q] = t1; a[2][q] = t2;
-            }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                b16x8 b[3];
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    const char* base = sl + p * FTW * WRB + lrow * WRB + (j * 32 + lcol) * 2;
-                    const b16x4 lo = __builtin_bit_cast(b16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)base));
-                    const b16x4 hi = __builtin_bit_cast(b16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + 4 * WRB)));
-                    b[p][0] = lo[0]; b[p][1] = lo[1]; b[p][2] = lo[2]; b[p][3] = lo[3];
-                    b[p][4] = hi[0]; b[p][5] = hi[1]; b[p][6] = hi[2]; b[p][7] = hi[3];
-                }
-                f32x16 c = acc[j];                     // small terms first (x3.hip)
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-                acc[j] = c;
-            }
-        };
-#pragma unroll
-        for (int u = 0; u < D; ++u) prefetch(u, r0 + u);
-        for (int y = r0; y < r1; y += D) {
-#pragma unroll
-            for (int u = 0; u < D; ++u) {
-                consume(u, u & 1, y + u < r1);
-                prefetch(u, y + u + D);
-            }
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) accs[wave][(r & 3) + 8 * (r >> 2) + 4 * lh][j * 32 + l31] = acc[j][r];
-    __syncthreads();
-    float* slab = partials + (long)blockIdx.x * 32 * 64;
-    for (int e = tid; e < 32 * 64; e += 256) {
-        const int i = e >> 6, co = e & 63;
-        slab[e] = accs[0][i][co] + accs[1][i][co] + accs[2][i][co] + accs[3][i][co];
-    }
+    sum_waves_store_slab(acc, (float (*)[32][64])dys, partials);
 }
 
 // dw[co][c][t] (+)= sum_k partials[k][c*9+t][co].  Block = 8 outputs (consecutive co of one im2col row: 32 contiguous bytes per
@@ -622,7 +561,7 @@ template <int C, bool STAT>
 __global__ __launch_bounds__(256, 3) void conv_first_fwd_stream_kernel(const float* __restrict__ x, long sN, int sC, int sH, int sW,
                                                                       int H, int W, const elt_t* __restrict__ w,
                                                                       elt_t* __restrict__ y, float* __restrict__ stat,
-                                                                      int strips, int segs, int seg_rows, int img_bytes) {
+                                                                      CfFwdPlan plan, int img_bytes) {
     constexpr int KS = (9 * C + 15) / 16;
     constexpr int PROWS = MTH + 2;                          // patch rows of a step
     // one patch buffer (floats): [c][10][34], then a ZERO AREA that padded k entries read: a lane's k -> patch index table is
@@ -637,9 +576,8 @@ __global__ __launch_bounds__(256, 3) void conv_first_fwd_stream_kernel(const flo
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform: the stores' row offset is a scalar operand
     const int l31 = lane & 31, lh = lane >> 5;
     const int item = blockIdx.x;
-    const int sx = item % strips, sy = (item / strips) % segs, img = item / (strips * segs);
-    const int x0 = sx * MTW, r0 = sy * seg_rows, r1 = min(H, r0 + seg_rows);
-    const int nsteps = (r1 - r0 + MTH - 1) / MTH;
+    const CfFwdItem it = conv_first_fwd_item(plan, H, item);
+    const int img = it.img, x0 = it.x0, r0 = it.r0, r1 = it.r1, nsteps = it.nsteps;
     constexpr int K = 9 * C;
     // every access to the image and to the output goes through a buffer resource of ONE image: an offset with bit 31 set fails
     // the range check (loads return 0, stores are dropped), so padding and ragged edges need no branch around a memory
@@ -655,7 +593,9 @@ __global__ __launch_bounds__(256, 3) void conv_first_fwd_stream_kernel(const flo
     for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int k = 16 * ks + 8 * lh + j, c = k / 9, tap = k - c * 9;
+            const int k = 16 * ks + 8 * lh + j;
+            int c, tap;
+            k_decode(k, c, tap);
             const bool kv = k < K;
             wf[ks][0][j] = kv ? w[((long)tap * 64 + l31) * 8 + c] : (elt_t)0.f;
             wf[ks][1][j] = kv ? w[((long)tap * 64 + 32 + l31) * 8 + c] : (elt_t)0.f;
@@ -758,19 +698,8 @@ __global__ __launch_bounds__(256, 3) void conv_first_fwd_stream_kernel(const flo
             for (int o = 8; o < 64; o <<= 1) { s1[j] += __shfl_xor(s1[j], o); s2[j] += __shfl_xor(s2[j], o); }
             if (lane < 8) { red[wave][0][lane * 8 + j] = s1[j]; red[wave][1][lane * 8 + j] = s2[j]; }
         }
-        __syncthreads();
-        if (tid < 128) {
-            const int q = tid >> 6, c = tid & 63;
-            stat[((long)item * 2 + q) * 64 + c] = red[0][q][c] + red[1][q][c] + red[2][q][c] + red[3][q][c];
-        }
+        sum_waves_store_stat(red, stat, item);
     }
-}
-
-// rows per block of the streaming forward: 64 where that still gives every CU four blocks, else shorter segments
-int stream_seg_rows(int N, int H, int W) {
-    int seg = 64;
-    while (seg > MTH && (long)N * cdiv(W, MTW) * cdiv(H, seg) < 1024) seg >>= 1;
-    return seg;
 }
 
 }  // namespace
@@ -780,22 +709,22 @@ bool conv_first_supported(const ustrun_src_t& s, int Cout) {
 }
 int conv_first_stat_rows(int N, int H, int W, int dtype) {
     if (dtype == USTRUN_D16 && (g_debug_flags & 16384)) return N * cdiv(H, MTH) * cdiv(W, MTW);
-    return dtype == USTRUN_D16 ? N * cdiv(H, stream_seg_rows(N, H, W)) * cdiv(W, MTW) : N * cdiv(H, FTH) * cdiv(W, FTW);
+    return dtype == USTRUN_D16 ? conv_first_fwd_grid(N, conv_first_fwd_plan(N, H, W)) : N * cdiv(H, FTH) * cdiv(W, FTW);
 }
 
 int conv_first_fwd(const ustrun_src_t& s, const void* w_fwd, int dtype, int N, void* y, float* stat, hipStream_t st) {
     if (dtype == USTRUN_D16 && !(g_debug_flags & 16384)) {       // im2col on the matrix cores, streaming form (round 4)
-        const int seg = stream_seg_rows(N, s.H, s.W), strips = cdiv(s.W, MTW), segs = cdiv(s.H, seg);
+        const CfFwdPlan plan = conv_first_fwd_plan(N, s.H, s.W);
         USTRUN_CHECK(s.C >= 1 && s.C <= CMAX, "conv_first_fwd: C=%d", s.C);
         const long img_elems = (long)(s.C - 1) * s.sC + (long)(s.H - 1) * s.sH + (long)(s.W - 1) * s.sW + 1;
         USTRUN_CHECK(img_elems * 4 < (1L << 31) && (long)s.H * s.W * 128 < (1L << 31), "conv_first_fwd: an image beyond 2^31 bytes");
-        dim3 grid(N * segs * strips), block(256);
+        dim3 grid(conv_first_fwd_grid(N, plan)), block(256);
 #define USTRUN_CFS(CC)                                                                                                              \
     do {                                                                                                                            \
         if (stat) hipLaunchKernelGGL((conv_first_fwd_stream_kernel<CC, true>), grid, block, 0, st, (const float*)s.ptr, (long)s.sN, (int)s.sC, \
-                                     (int)s.sH, (int)s.sW, s.H, s.W, (const elt_t*)w_fwd, (elt_t*)y, stat, strips, segs, seg, (int)(img_elems * 4)); \
+                                     (int)s.sH, (int)s.sW, s.H, s.W, (const elt_t*)w_fwd, (elt_t*)y, stat, plan, (int)(img_elems * 4)); \
         else hipLaunchKernelGGL((conv_first_fwd_stream_kernel<CC, false>), grid, block, 0, st, (const float*)s.ptr, (long)s.sN, (int)s.sC,   \
-                                (int)s.sH, (int)s.sW, s.H, s.W, (const elt_t*)w_fwd, (elt_t*)y, stat, strips, segs, seg, (int)(img_elems * 4));     \
+                                (int)s.sH, (int)s.sW, s.H, s.W, (const elt_t*)w_fwd, (elt_t*)y, stat, plan, (int)(img_elems * 4));     \
     } while (0)
         if (s.C == 1) USTRUN_CFS(1); else if (s.C == 2) USTRUN_CFS(2); else if (s.C == 3) USTRUN_CFS(3); else USTRUN_CFS(4);
 #undef USTRUN_CFS
@@ -813,82 +742,56 @@ int conv_first_fwd(const ustrun_src_t& s, const void* w_fwd, int dtype, int N, v
         return 0;
     }
     const int tx = cdiv(s.W, FTW), ty = cdiv(s.H, FTH);
-    if (false)
-        hipLaunchKernelGGL(conv_first_fwd_kernel<2>, dim3(N * ty * tx), dim3(256), 0, st, (const float*)s.ptr, (long)s.sN, (long)s.sC,
-                           (long)s.sH, (long)s.sW, s.C, s.H, s.W, w_fwd, 1, (float*)y, stat, tx, ty);
-    else
-        hipLaunchKernelGGL(conv_first_fwd_kernel<4>, dim3(N * ty * tx), dim3(256), 0, st, (const float*)s.ptr, (long)s.sN, (long)s.sC,
-                           (long)s.sH, (long)s.sW, s.C, s.H, s.W, w_fwd, 0, (float*)y, stat, tx, ty);
+    hipLaunchKernelGGL(conv_first_fwd_kernel, dim3(N * ty * tx), dim3(256), 0, st, (const float*)s.ptr, (long)s.sN, (long)s.sC,
+                       (long)s.sH, (long)s.sW, s.C, s.H, s.W, (const float*)w_fwd, (float*)y, stat, tx, ty);
     USTRUN_LAUNCH_CHECK("conv_first_fwd");
     return 0;
 }
 
-int64_t conv_first_wgrad_partials_bytes() { return (int64_t)1024 * 32 * 64 * sizeof(float); }
+int64_t conv_first_wgrad_partials_bytes() { return (int64_t)(CF_WG_ITEMS / CF_WG_WAVES) * 32 * 64 * sizeof(float); }
+
+namespace {
+
+int launch_reduce(const float* partials, int slabs, int C, float* dw, int accumulate, hipStream_t st) {
+    hipLaunchKernelGGL(conv_first_wgrad_reduce_kernel, dim3(cdiv(64 * C * 9, 8)), dim3(1024), 0, st, partials, slabs, C, dw, accumulate);
+    USTRUN_LAUNCH_CHECK("conv_first_wgrad_reduce");
+    return 0;
+}
+
+// plan and launch the streaming kernel (the caller has asked conv_first_wgrad_stream_ok), then the slab reduce
+template <typename Op>
+int launch_wgrad_stream(const ustrun_src_t& s, const void* dy, int N, float* dw, int accumulate, float* partials, hipStream_t st) {
+    const CfWgradPlan p = conv_first_wgrad_plan(N, s.H, s.W);
+    const auto kernel = conv_first_wgrad_stream_kernel<Op, 4>;
+    if (Op::LDS > 65536) USTRUN_TRY(ensure_dynamic_lds((const void*)kernel, Op::LDS, Op::NAME));
+    hipLaunchKernelGGL(kernel, dim3(p.blocks), dim3(256), Op::LDS, st, (const float*)s.ptr, (int)s.sN, (int)s.sC, (int)s.sH, s.C, s.H, s.W,
+                       (int)((long)N * s.sN * 4), (const typename Op::dy_t*)dy, (int)((long)N * s.H * s.W * Op::PXB), partials, p.strips,
+                       p.nseg, p.seg_rows, (int)p.items);
+    USTRUN_LAUNCH_CHECK(Op::NAME);
+    return launch_reduce(partials, p.blocks, s.C, dw, accumulate, st);
+}
+
+}  // namespace
 
 int conv_first_wgrad(const ustrun_src_t& s, const void* dy, int dy_esz, int N, float* dw, int accumulate, float* partials,
                      int64_t partials_bytes, hipStream_t st, bool x3) {
     USTRUN_CHECK(partials_bytes >= conv_first_wgrad_partials_bytes(), "conv_first_wgrad: partials too small");
+    USTRUN_CHECK(dy_esz == (x3 ? 4 : 2), "conv_first_wgrad: %d-byte dY", dy_esz);
+    const bool stream_ok = conv_first_wgrad_stream_ok(s, N, s.H, s.W, dy_esz);
+    if (x3) {                           // dtype USTRUN_F32X3: f32 dY, three-term products
+        USTRUN_CHECK(stream_ok, "conv_first_wgrad: layout outside the streaming kernel's range");
+        return launch_wgrad_stream<WgOpX3>(s, dy, N, dw, accumulate, partials, st);
+    }
+    // (ustrun_debug_flags bit 28: the tile kernel of rounds 1-4, for A/B runs)
+    if (stream_ok && !(g_debug_flags & (1 << 28))) return launch_wgrad_stream<WgOp16>(s, dy, N, dw, accumulate, partials, st);
     const int tx = cdiv(s.W, FTW), ty = cdiv(s.H, FTH), ttotal = N * ty * tx;
     int blocks = ttotal < 1024 ? ttotal : 1024;
     const int per = cdiv(ttotal, blocks);
     blocks = cdiv(ttotal, per);
-    // (ustrun_debug_flags bit 28: the tile kernel of rounds 1-4, for A/B runs)
-    if (dy_esz == 4 && x3) {            // dtype USTRUN_F32X3: f32 dY, three-term products
-        const long xb = (long)N * s.sN * 4, db = (long)N * s.H * s.W * 64 * 4;
-        USTRUN_CHECK(s.sW == 1 && s.f32 && xb < (1L << 31) - 64 && db < (1L << 31) - 64 && s.sN == (int64_t)s.C * s.sC &&
-                     s.sC == (int64_t)s.H * s.sH, "conv_first_wgrad: layout outside the streaming kernel's range");
-        const int strips = cdiv(s.W, FTW);
-        long segs = 4096 / ((long)N * strips);
-        if (segs > s.H / 8) segs = s.H / 8;
-        if (segs < 1) segs = 1;
-        const int seg_rows = cdiv(s.H, segs);
-        const int nseg = cdiv(s.H, seg_rows);
-        const long items = (long)N * strips * nseg;
-        USTRUN_CHECK(items <= 4096, "conv_first_wgrad: %ld strip segments", items);
-        blocks = cdiv(items, 4);
-        const int lds = 4 * 2 * 3 * FTW * WRB;
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv_first_wgrad_stream_x3_kernel<4>, lds, "conv_first_wgrad_x3"));
-        hipLaunchKernelGGL(conv_first_wgrad_stream_x3_kernel<4>, dim3(blocks), dim3(256), lds, st, (const float*)s.ptr, (int)s.sN, (int)s.sC,
-                           (int)s.sH, s.C, s.H, s.W, (int)xb, (const float*)dy, (int)db, partials, strips, nseg, seg_rows, (int)items);
-        USTRUN_LAUNCH_CHECK("conv_first_wgrad_x3");
-        hipLaunchKernelGGL(conv_first_wgrad_reduce_kernel, dim3(cdiv(64 * s.C * 9, 8)), dim3(1024), 0, st, partials, blocks, s.C, dw,
-                           accumulate);
-        USTRUN_LAUNCH_CHECK("conv_first_wgrad_reduce");
-        return 0;
-    }
-    const long xbytes = (long)N * s.sN * 4, dybytes = (long)N * s.H * s.W * 64 * 2;
-    if (dy_esz == 2 && s.sW == 1 && s.f32 && !(g_debug_flags & (1 << 28)) && xbytes < (1L << 31) - 64 && dybytes < (1L << 31) - 64 &&
-        s.sN == (int64_t)s.C * s.sC && s.sC == (int64_t)s.H * s.sH) {
-        const int strips = cdiv(s.W, FTW);
-        long segs = 4096 / ((long)N * strips);
-        if (segs > s.H / 8) segs = s.H / 8;
-        if (segs < 1) segs = 1;
-        const int seg_rows = cdiv(s.H, segs);
-        const int nseg = cdiv(s.H, seg_rows);
-        const long items = (long)N * strips * nseg;
-        if (items <= 4096) {
-            blocks = cdiv(items, 4);
-            hipLaunchKernelGGL(conv_first_wgrad_stream_kernel<4>, dim3(blocks), dim3(256), 0, st, (const float*)s.ptr, (int)s.sN, (int)s.sC,
-                               (int)s.sH, s.C, s.H, s.W, (int)xbytes, (const elt_t*)dy, (int)dybytes, partials, strips, nseg, seg_rows,
-                               (int)items);
-            USTRUN_LAUNCH_CHECK("conv_first_wgrad_stream");
-            hipLaunchKernelGGL(conv_first_wgrad_reduce_kernel, dim3(cdiv(64 * s.C * 9, 8)), dim3(1024), 0, st, partials, blocks, s.C, dw,
-                               accumulate);
-            USTRUN_LAUNCH_CHECK("conv_first_wgrad_reduce");
-            return 0;
-        }
-    }
-    if (dy_esz == 2)
-        hipLaunchKernelGGL(conv_first_wgrad_kernel<2>, dim3(blocks), dim3(256), 0, st, (const float*)s.ptr, (long)s.sN, (long)s.sC,
-                           (long)s.sH, (long)s.sW, s.C, s.H, s.W, (const float*)dy, partials, tx, ty, ttotal, per);
-    else
-        hipLaunchKernelGGL(conv_first_wgrad_kernel<4>, dim3(blocks), dim3(256), 0, st, (const float*)s.ptr, (long)s.sN, (long)s.sC,
-                           (long)s.sH, (long)s.sW, s.C, s.H, s.W, (const float*)dy, partials, tx, ty, ttotal, per);
+    hipLaunchKernelGGL(conv_first_wgrad_kernel, dim3(blocks), dim3(256), 0, st, (const float*)s.ptr, (long)s.sN, (long)s.sC, (long)s.sH,
+                       (long)s.sW, s.C, s.H, s.W, (const elt_t*)dy, partials, tx, ty, ttotal, per);
     USTRUN_LAUNCH_CHECK("conv_first_wgrad");
-    hipLaunchKernelGGL(conv_first_wgrad_reduce_kernel, dim3(cdiv(64 * s.C * 9, 8)), dim3(1024), 0, st, partials, blocks, s.C, dw,
-                       accumulate);
-    USTRUN_LAUNCH_CHECK("conv_first_wgrad_reduce");
-    return 0;
+    return launch_reduce(partials, blocks, s.C, dw, accumulate, st);
 }
 
 }  // namespace ustrun

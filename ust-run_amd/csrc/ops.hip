@@ -2,6 +2,7 @@
 // implicit-GEMM / weight-gradient kernels, plus the weight packing kernels.
 #include "common.h"
 #include "loader.h"
+#include "conv_first_plan.h"
 #include <stdlib.h>
 
 namespace ustrun {
@@ -480,9 +481,7 @@ extern "C" int ustrun_conv3x3_wgrad(const ustrun_src_t* srcs, int nsrc, const vo
     }
     // (dtype USTRUN_F32X3's first convolution: the streaming kernel with three-term products)
     if (dtype == USTRUN_F32X3 && nsrc == 1 && conv_first_supported(srcs[0], Cout) && srcs[0].H == H && srcs[0].W == W && srcs[0].f32 &&
-        9 * srcs[0].C <= 32 && srcs[0].sW == 1 && srcs[0].sN == (int64_t)srcs[0].C * srcs[0].sC && srcs[0].sC == (int64_t)H * srcs[0].sH &&
-        (int64_t)N * H * W * 256 < (1LL << 31) - 64 && (int64_t)N * srcs[0].sN * 4 < (1LL << 31) - 64 && (int64_t)N * cdiv(W, 16) <= 4096 &&
-        !(g_debug_flags & (1 << 29)))
+        9 * srcs[0].C <= 32 && conv_first_wgrad_stream_ok(srcs[0], N, H, W, 4) && !(g_debug_flags & (1 << 29)))
         return conv_first_wgrad(srcs[0], dy, 4, N, dw, accumulate, partials, partials_bytes, (hipStream_t)s, true);
     if (dtype == USTRUN_F32X3 && wgrad_x3_supported(a)) {        // all nine taps per block, operands split at staging (x3.hip)
         int per;

@@ -1,5 +1,5 @@
-// tn_gemm.h -- what the weight-gradient kernels share (wgrad_bf16, wgradT_bf16, wgrad_tap_bf16, wgrad_tap_x3, wgrad_halo_bf16 and
-// the all-taps kernel of x3.hip).  Each is a "TN" GEMM over pixels: both operands sit pixel-major ([pixel][channel]) in LDS, the
+// tn_gemm.h -- what the weight-gradient kernels share (wgrad_bf16, wgradT_bf16, wgrad_tap_bf16, wgrad_tap_x3, wgrad_halo_bf16, the
+// all-taps kernel of x3.hip and conv_first).  Each is a "TN" GEMM over pixels: both operands sit pixel-major ([pixel][channel]) in LDS, the
 // K-major MFMA fragments come from the transposing LDS read ds_read_b64_tr_b16 (4 rows x 16 columns per 16-lane group, delivered
 // column-major), blocks are renumbered so that one pixel slice stays on one XCD and pixels are decomposed with a float
 // reciprocal.  The index helpers are __host__ __device__: a CPU program checks

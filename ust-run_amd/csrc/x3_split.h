@@ -1,4 +1,4 @@
-// x3_split.h -- the arithmetic of dtype USTRUN_F32X3 shared by its kernels (x3.hip, wgrad_tap_x3.hip): an f32 value as three bf16
+// x3_split.h -- the arithmetic of dtype USTRUN_F32X3 shared by its kernels (x3.hip, wgrad_tap_x3.hip, conv_first.hip): an f32 value as three bf16
 // terms, a product of two such values as six bf16 MFMAs with f32 accumulation (see x3.hip's header).
 #pragma once
 #include "common.h"
