@@ -450,6 +450,68 @@ def test_conv3x3_bf16_mfma(n, ci, co, h, w, exact):
     assert rel(dw.cpu(), wr.grad) < tol
 
 
+@pytest.mark.parametrize("dt,tdt", [(1, torch.bfloat16), (2, torch.float16)])
+def test_conv3x3_loader_affine_relu_pool_concat_pad_16bit(dt, tdt):
+    """test_conv3x3_loader_affine_relu_pool_concat_pad on 16-bit storage, where 24 output channels keep every launch on the generic
+    implicit-GEMM kernel and M = 286 leaves a ragged last tile at both tile heights (128 and 256 rows): the pooled source with
+    BatchNorm statistics (negative scales included), the concat with a pad offset, and the input gradient split over a c0-channel
+    destination and an offset window of c1 channels.  Small-integer data is exact in both element types and sums exactly in f32."""
+    l = L()
+    lib = l.lib()
+    g = torch.Generator().manual_seed(2)
+    n, c0, c1, co, h, w = 2, 16, 8, 24, 11, 13
+    ints = lambda lo, hi, *shape: torch.randint(lo, hi + 1, shape, generator=g).float()
+    r = lambda t: t.to(tdt).float()                      # what an exact f32 result reads back as
+    dev = lambda t: nhwc(t).to(tdt)
+
+    def pack(wt):
+        k = 9 * ((wt.shape[1] + 7) // 8 * 8) * ((wt.shape[0] + 7) // 8 * 8)
+        wf, wd = torch.zeros(k, dtype=tdt, device="cuda"), torch.zeros(k, dtype=tdt, device="cuda")
+        wg = wt.contiguous().cuda()
+        l.check(lib.ustrun_pack_conv3x3(wg.data_ptr(), wt.shape[0], wt.shape[1], wf.data_ptr(), wd.data_ptr(), dt, None))
+        return wf, wd
+
+    # pooled single source, with statistics
+    ys = ints(-3, 3, n, c0, 2 * h + 1, 2 * w)
+    sc = ints(1, 2, c0) * (2 * ints(0, 1, c0) - 1)
+    sh = ints(-1, 1, c0)
+    wt = ints(-1, 1, co, c0, 3, 3)
+    a = F.max_pool2d(torch.relu(ys * sc[None, :, None, None] + sh[None, :, None, None]), 2)
+    ref = r(F.conv2d(a, wt, None, 1, 1))
+    wf, _ = pack(wt)
+    yg, scg, shg = dev(ys), sc.cuda(), sh.cuda()
+    src = l.nhwc_src(yg.data_ptr(), c0, 2 * h + 1, 2 * w, scg.data_ptr(), shg.data_ptr(), relu=1, pool=1)
+    out = torch.full((n, h, w, co), 7.0, device="cuda", dtype=tdt)
+    stat = torch.zeros(lib.ustrun_conv_mtiles(n, h, w, co), 2, co, device="cuda")
+    l.check(lib.ustrun_conv3x3_fwd(C.byref(src), 1, wf.data_ptr(), n, h, w, co, out.data_ptr(), stat.data_ptr(), dt, None))
+    stored = from_nhwc(out.float())
+    assert rel(stored, ref) < 1e-6
+    assert rel(stat[:, 0].sum(0).cpu(), stored.sum((0, 2, 3))) < 1e-6
+    assert rel(stat[:, 1].sum(0).cpu(), stored.square().sum((0, 2, 3))) < 1e-6
+    # concat [skip (affine+relu), up (offset-padded, smaller extent)]
+    skip, up = ints(-3, 3, n, c0, h, w), ints(-3, 3, n, c1, h - 3, w - 2)
+    wt2 = ints(-1, 1, co, c0 + c1, 3, 3)
+    a2 = torch.cat([torch.relu(skip * sc[None, :, None, None] + sh[None, :, None, None]), F.pad(up, [1, 1, 1, 2])], 1)
+    ref2 = r(F.conv2d(a2, wt2, None, 1, 1))
+    wf2, wd2 = pack(wt2)
+    sg, ug = dev(skip), dev(up)
+    srcs = (l.Src * 2)(l.nhwc_src(sg.data_ptr(), c0, h, w, scg.data_ptr(), shg.data_ptr(), relu=1),
+                       l.nhwc_src(ug.data_ptr(), c1, h - 3, w - 2, off=(1, 1)))
+    out2 = torch.full((n, h, w, co), 7.0, device="cuda", dtype=tdt)
+    l.check(lib.ustrun_conv3x3_fwd(srcs, 2, wf2.data_ptr(), n, h, w, co, out2.data_ptr(), None, dt, None))
+    assert rel(from_nhwc(out2.float()), ref2) < 1e-6
+    # input gradient of that convolution: c0 channels whole, c1 channels into the window the padded source came from
+    dy = ints(-3, 3, n, co, h, w)
+    gref = r(F.conv_transpose2d(dy, wt2, None, 1, 1))
+    dyg = dev(dy)
+    d0 = torch.full((n, h, w, c0), 7.0, device="cuda", dtype=tdt)
+    d1 = torch.full((n, h - 3, w - 2, c1), 7.0, device="cuda", dtype=tdt)
+    l.check(lib.ustrun_conv3x3_dgrad(dyg.data_ptr(), wd2.data_ptr(), n, h, w, co, c0 + c1, d0.data_ptr(), c0, d1.data_ptr(), h - 3, w - 2, 1, 1,
+                                     dt, None))
+    assert rel(from_nhwc(d0.float()), gref[:, :c0]) < 1e-6
+    assert rel(from_nhwc(d1.float()), gref[:, c0:, 1:h - 2, 1:w - 1]) < 1e-6
+
+
 @pytest.mark.parametrize("elt", ["bf16", "f16"])
 @pytest.mark.parametrize("flags", [0, 1 << 28])
 @pytest.mark.parametrize("n,c,h,w", [(2, 3, 16, 32), (1, 1, 19, 37), (2, 4, 9, 70), (3, 3, 40, 33), (4, 3, 136, 96), (16, 1, 72, 100),

@@ -62,12 +62,7 @@ __global__ __launch_bounds__(256, 2) void convT_bf16_kernel(const IgemmArgs a, c
     char* As = smem;
     char* Bs = smem + 2 * ABYTES;
 
-    const int ntiles = mt_total * nt_total;
-    int bid = blockIdx.x;
-    {
-        const int q = ntiles / 8, r = ntiles % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_linear(blockIdx.x, mt_total * nt_total);
     const int mtile = bid / nt_total, ntile = bid % nt_total;
     const int n0 = ntile * BN;
     const int m0 = mtile * BM;                  // (M < 2^29: the launcher checks)

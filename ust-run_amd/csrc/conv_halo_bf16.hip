@@ -117,12 +117,7 @@ __global__ __launch_bounds__(256, (TH * TW * BN >= 512 * 64 && BN == 64 ? 1 : 2)
     const int IS = LIN ? (a.Ho + 1) * RP : 1;                                   // LIN: positions per image
     const int lin_full = LIN ? a.N / tiles_y : 0;                               //      full passes
     const int mt_total = LIN ? lin_full * tiles_x + ((a.N - lin_full * tiles_y) * IS + TM - 1) / TM : a.N * tiles_y * tiles_x;
-    const int ntiles = mt_total * nt_total;
-    int bid = blockIdx.x;
-    {
-        const int q = ntiles / 8, r = ntiles % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_linear(blockIdx.x, mt_total * nt_total);
     const int mtile = bid / nt_total, ntile = bid % nt_total;
     const int n0 = ntile * BN;
     const int lpass = LIN ? min(mtile / tiles_x, lin_full) : 0;

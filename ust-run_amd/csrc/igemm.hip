@@ -13,8 +13,7 @@
 // accumulators (bitwise an f32 fmaf chain, MI355X_MICROARCH "Matrix cores").  K is consumed in
 // stages of 32 channels: global -> registers (prefetched under the previous stage's MFMAs) ->
 // transform -> LDS (A stored k-major so that lanes read consecutive pixels, B row-major) -> MFMA.
-#include "common.h"
-#include "loader.h"
+#include "igemm_tile.h"
 #include <stdlib.h>
 
 namespace ustrun {
@@ -22,8 +21,6 @@ namespace ustrun {
 namespace {
 
 constexpr int BK = 32;
-
-struct RowInfo { int n; int yx; };
 
 template <int WM, int WN, bool POOL>
 __global__ __launch_bounds__(256, 2) void igemm_f32_kernel(const IgemmArgs a, const int mt_total, const int nt_total) {
@@ -41,14 +38,8 @@ __global__ __launch_bounds__(256, 2) void igemm_f32_kernel(const IgemmArgs a, co
     float* Bs = As + A_FLOATS;
     RowInfo* rowinfo = (RowInfo*)(Bs + BK * BN);
 
-    // ---- XCD-aware tile id: consecutive hardware block ids round-robin over the 8 XCDs, so give
-    // each XCD a contiguous run of tiles (n-tiles of one m-tile adjacent -> A panel shared in L2).
-    const int ntiles = mt_total * nt_total;
-    int bid = blockIdx.x;
-    {
-        const int q = ntiles / 8, r = ntiles % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    // XCD-aware tile id: n-tiles of one m-tile adjacent -> A panel shared in the XCD's L2
+    const int bid = xcd_linear(blockIdx.x, mt_total * nt_total);
     const int mtile = bid / nt_total, ntile = bid % nt_total;
     const int z = blockIdx.y;
     const int n0 = ntile * BN;
@@ -56,19 +47,7 @@ __global__ __launch_bounds__(256, 2) void igemm_f32_kernel(const IgemmArgs a, co
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
 
-    for (int r = tid; r < BM; r += 256) {
-        long m = (long)mtile * BM + r;
-        RowInfo ri;
-        if (m < a.M) {
-            int hw = a.Hb * a.Wb;
-            int n = (int)(m / hw);
-            int rem = (int)(m - (long)n * hw);
-            int by = rem / a.Wb;
-            ri.n = n; ri.yx = (by << 16) | (rem - by * a.Wb);
-        } else { ri.n = -1; ri.yx = 0; }
-        rowinfo[r] = ri;
-    }
-    __syncthreads();
+    fill_row_table<BM>(rowinfo, a, mtile, tid);
 
     const int a_c4 = tid & 7, a_r0 = tid >> 3;
     const int b_n4 = tid % BQ, b_k0 = tid / BQ;
@@ -77,60 +56,14 @@ __global__ __launch_bounds__(256, 2) void igemm_f32_kernel(const IgemmArgs a, co
     const int nchunk = (a.Cin + BK - 1) / BK;
     const int nstage = a.nseg * nchunk;
 
-    f32x4 av[AR][NP];
-    f32x4 asc, ash;
+    f32x4 av[AR][NP], asc, ash;
     unsigned aok;
     int a_relu;
     f32x4 bv[BR];
 
     auto load_stage = [&](int s) {
         const int seg = s / nchunk, c0 = (s - seg * nchunk) * BK;
-        const int dy = a.d0 + (seg / a.segw) * a.dstep, dx = a.d0 + (seg % a.segw) * a.dstep;
-        const int cg = c0 + 4 * a_c4;
-        aok = 0;
-        asc = (f32x4){1.f, 1.f, 1.f, 1.f}; ash = (f32x4){0.f, 0.f, 0.f, 0.f}; a_relu = 0;
-        if (vecA) {
-            const bool second = (a.nsrc == 2 && cg >= a.src[0].C);
-            const SrcDev S = pick_src(a.src[0], a.src[1], second);
-            const int cl = cg - (second ? a.src[0].C : 0);
-            const bool cok = cg < a.Cin;
-            if (cok && S.scale) { asc = *(const f32x4*)(S.scale + cl); ash = *(const f32x4*)(S.shift + cl); }
-            a_relu = S.relu;
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                RowInfo ri = rowinfo[a_r0 + 32 * i];
-                const int ly = (ri.yx >> 16) * a.s_in + dy - S.off_y;
-                const int lx = (ri.yx & 0xffff) * a.s_in + dx - S.off_x;
-                const bool ok = cok && ri.n >= 0 && ly >= 0 && ly < S.LH && lx >= 0 && lx < S.LW;
-                if (ok) {
-                    aok |= 1u << i;
-                    if (POOL) {
-                        const float* p = S.ptr + ri.n * S.sN + (long)(2 * ly) * S.sH + (long)(2 * lx) * S.sW + cl;
-                        av[i][0] = *(const f32x4*)p;
-                        av[i][1 % NP] = *(const f32x4*)(p + S.sW);
-                        av[i][2 % NP] = *(const f32x4*)(p + S.sH);
-                        av[i][3 % NP] = *(const f32x4*)(p + S.sH + S.sW);
-                    } else {
-                        av[i][0] = *(const f32x4*)(S.ptr + ri.n * S.sN + (long)ly * S.sH + (long)lx * S.sW + cl);
-                    }
-                }
-            }
-        } else {
-            // scalar path (first layer with C = 1/3, tiny test nets): the transform is applied
-            // here and the write pass only copies.
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                RowInfo ri = rowinfo[a_r0 + 32 * i];
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (ri.n >= 0) {
-                    const int iy = (ri.yx >> 16) * a.s_in + dy, ix = (ri.yx & 0xffff) * a.s_in + dx;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (cg + j < a.Cin) v[j] = load_elem(a.src[0], a.src[1], a.nsrc, ri.n, iy, ix, cg + j);
-                }
-                av[i][0] = v;
-            }
-        }
+        load_a_stage<4, POOL, AR, 32>(av, asc, ash, a_relu, aok, a, rowinfo, vecA, seg, c0 + 4 * a_c4, a_r0);
         // B tile: W[slice][c0 + k][n0 + 4*b_n4 ..]
         const float* wb = a.W + ((long)(seg + z) * a.Cin) * a.Cout;
 #pragma unroll
@@ -152,20 +85,7 @@ __global__ __launch_bounds__(256, 2) void igemm_f32_kernel(const IgemmArgs a, co
     auto write_stage = [&]() {
 #pragma unroll
         for (int i = 0; i < AR; ++i) {
-            f32x4 v = av[i][0];
-            if (vecA) {
-                v = v * asc + ash;
-                if (a_relu) v = relu4(v);
-                if (POOL) {
-#pragma unroll
-                    for (int q = 1; q < NP; ++q) {
-                        f32x4 t = av[i][q] * asc + ash;
-                        if (a_relu) t = relu4(t);
-                        v = max4(v, t);
-                    }
-                }
-                if (!((aok >> i) & 1u)) v = (f32x4){0.f, 0.f, 0.f, 0.f};
-            }
+            const f32x4 v = activate(av[i], asc, ash, a_relu, (aok >> i) & 1u, vecA);
             const int row = a_r0 + 32 * i;
 #pragma unroll
             for (int j = 0; j < 4; ++j) As[(4 * a_c4 + j) * LDA + row] = v[j];
@@ -204,60 +124,7 @@ __global__ __launch_bounds__(256, 2) void igemm_f32_kernel(const IgemmArgs a, co
         __syncthreads();
     }
 
-    // ---- epilogue: D[row = pixel][col = channel]; col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-    const int oyz = z >> 1, oxz = z & 1;
-    const int C1 = a.Cout - a.C0;
-    float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = n0 + wn * 64 + j * 32 + l31;
-        const bool cok = col < a.Cout;
-        const float bias = (a.bias && cok) ? a.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const RowInfo ri = rowinfo[row];
-                if (ri.n >= 0 && cok) {
-                    const float v = acc[i][j][r] + bias;
-                    const int oy = (ri.yx >> 16) * a.s_out + oyz, ox = (ri.yx & 0xffff) * a.s_out + oxz;
-                    if (col < a.C0) {
-                        a.out0[(((long)ri.n * a.Ho + oy) * a.Wo + ox) * a.C0 + col] = v;
-                    } else {
-                        const int y1 = oy - a.o1y, x1 = ox - a.o1x;
-                        if (y1 >= 0 && y1 < a.H1 && x1 >= 0 && x1 < a.W1)
-                            a.out1[(((long)ri.n * a.H1 + y1) * a.W1 + x1) * C1 + (col - a.C0)] = v;
-                    }
-                    s1[j] += v; s2[j] += v * v;
-                }
-            }
-        }
-    }
-    if (a.stat) {
-        // fixed-order tree: lane halves, then the WM waves that share these columns
-        float* red = As;  // [WM][2][BN], free after the final barrier of the main loop
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            s1[j] += __shfl_xor(s1[j], 32);
-            s2[j] += __shfl_xor(s2[j], 32);
-            if (lh == 0) {
-                red[(wm * 2 + 0) * BN + wn * 64 + j * 32 + l31] = s1[j];
-                red[(wm * 2 + 1) * BN + wn * 64 + j * 32 + l31] = s2[j];
-            }
-        }
-        __syncthreads();
-        // one stat row per 128 pixels whatever the tile height, so that the row count does not
-        // depend on the tile configuration (ustrun_conv_mtiles)
-        constexpr int HALVES = WM / 2;
-        const int stat_rows = (int)((a.M + 127) / 128);
-        for (int t = tid; t < HALVES * 2 * BN; t += 256) {
-            const int h = t / (2 * BN), q = (t / BN) % 2, c = t % BN;
-            const float v = red[((2 * h) * 2 + q) * BN + c] + red[((2 * h + 1) * 2 + q) * BN + c];
-            const int srow = mtile * HALVES + h;
-            if (srow < stat_rows && n0 + c < a.Cout) a.stat[((long)srow * 2 + q) * a.Cout + n0 + c] = v;
-        }
-    }
+    igemm_epilogue<WM, WN, false>(a, acc, rowinfo, As, mtile, n0, z, tid);
 }
 
 template <int WM, int WN, bool POOL>
@@ -273,10 +140,8 @@ int launch_cfg(const IgemmArgs& a, hipStream_t st) {
 
 }  // namespace
 
-// M-tile height the launcher will pick for this problem (must agree with igemm_launch)
-static int pick_bm(int Cout) { return (Cout > 64) ? 128 : 256; }
-
-int igemm_mtiles(int64_t M, int Cout) { (void)Cout; return cdiv(M, 128); }
+// one statistics row per 128 pixels (igemm_epilogue) whatever Cout and the tile it selects: the parameter stays for the callers
+int igemm_mtiles(int64_t M, int) { return cdiv(M, 128); }
 
 // stat rows actually written by the kernel igemm_launch will pick
 int igemm_stat_rows_used(const IgemmArgs& a, int dtype) {
@@ -292,10 +157,10 @@ int igemm_launch(const IgemmArgs& a, int dtype, hipStream_t st) {
     USTRUN_CHECK(a.Hb < 65536 && a.Wb < 65536, "igemm: extent too large");
     USTRUN_CHECK(a.nseg >= 1 && a.nseg <= 49 && a.nz >= 1 && a.nz <= 4, "igemm: bad segment/parity count");
     int csum = 0;
-    bool pool = false;
-    for (int i = 0; i < a.nsrc; ++i) { csum += a.src[i].C; pool |= a.src[i].pool != 0; }
+    for (int i = 0; i < a.nsrc; ++i) csum += a.src[i].C;
+    const IgemmTile tile = igemm_pick_tile(a);
     USTRUN_CHECK(csum == a.Cin, "igemm: source channels %d != Cin %d", csum, a.Cin);
-    USTRUN_CHECK(!pool || a.nsrc == 1, "igemm: pooled source cannot be concatenated");
+    USTRUN_CHECK(!tile.pool || a.nsrc == 1, "igemm: pooled source cannot be concatenated");
     // algorithmic cost of this launch: every stored input/weight/output element touched once
     double in_elems = 0;
     for (int i = 0; i < a.nsrc; ++i) in_elems += (double)a.N * a.src[i].H * a.src[i].W * a.src[i].C;
@@ -322,8 +187,8 @@ int igemm_launch(const IgemmArgs& a, int dtype, hipStream_t st) {
         else rc = igemm_launch_bf16(a, st);
     } else if (dtype == USTRUN_F32X3 && igemm_x3_supported(a) && (!grouped || conv3x3_x3_supported(a))) {     // three-term bf16 products (x3.hip)
         rc = igemm_x3_launch(a, st);
-    } else if (pick_bm(a.Cout) == 128 || pool) {   // (narrow outputs with a pooled source only occur in tiny test nets)
-        rc = pool ? launch_cfg<2, 2, true>(a, st) : launch_cfg<2, 2, false>(a, st);
+    } else if (tile.wm == 2) {
+        rc = tile.pool ? launch_cfg<2, 2, true>(a, st) : launch_cfg<2, 2, false>(a, st);
     } else {
         rc = launch_cfg<4, 1, false>(a, st);
     }

@@ -3,14 +3,10 @@
 // applies the BatchNorm/ReLU/pool/concat transform in f32, rounds to bf16 (RNE) and stores a
 // K-contiguous, XOR-swizzled A tile in LDS; weights are pre-packed in bf16 as [slice][K/8][N][8] so
 // that a lane's 8 consecutive K values are one 16-byte LDS read with no conflicts.
-#include "common.h"
-#include "loader.h"
+#include "igemm_tile.h"
 
 namespace ustrun {
 namespace {
-
-
-struct RowInfo { int n; int yx; };
 
 template <int WM, int WN, bool POOL>
 __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const IgemmArgs a, const int mt_total, const int nt_total) {
@@ -29,31 +25,14 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const IgemmArgs a, c
     char* Bs = smem + BM * ROWB;            // [BK/8][BN][8] bf16
     RowInfo* rowinfo = (RowInfo*)(Bs + BCH * 16);
 
-    const int ntiles = mt_total * nt_total;
-    int bid = blockIdx.x;
-    {
-        const int q = ntiles / 8, r = ntiles % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_linear(blockIdx.x, mt_total * nt_total);
     const int mtile = bid / nt_total, ntile = bid % nt_total;
     const int z = blockIdx.y;
     const int n0 = ntile * BN;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
 
-    for (int r = tid; r < BM; r += 256) {
-        long m = (long)mtile * BM + r;
-        RowInfo ri;
-        if (m < a.M) {
-            int hw = a.Hb * a.Wb;
-            int n = (int)(m / hw);
-            int rem = (int)(m - (long)n * hw);
-            int by = rem / a.Wb;
-            ri.n = n; ri.yx = (by << 16) | (rem - by * a.Wb);
-        } else { ri.n = -1; ri.yx = 0; }
-        rowinfo[r] = ri;
-    }
-    __syncthreads();
+    fill_row_table<BM>(rowinfo, a, mtile, tid);
 
     auto swz = [](int row) { return BK == 64 ? ((row >> 1) & 7) : ((row >> 2) & 3); };
 
@@ -64,58 +43,14 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const IgemmArgs a, c
     const int K8 = (a.Cin + 7) / 8;         // packed K octets per slice
     const elt_t* Wp = (const elt_t*)a.W;
 
-    f32x4 av[AR][NP];
-    f32x4 asc, ash;
+    f32x4 av[AR][NP], asc, ash;
     unsigned aok;
     int a_relu;
     bf16x8 bv[BR];
 
     auto load_stage = [&](int s) {
         const int seg = s / nchunk, c0 = (s - seg * nchunk) * BK;
-        const int dy = a.d0 + (seg / a.segw) * a.dstep, dx = a.d0 + (seg % a.segw) * a.dstep;
-        const int cg = c0 + 4 * a_c4;
-        aok = 0;
-        asc = (f32x4){1.f, 1.f, 1.f, 1.f}; ash = (f32x4){0.f, 0.f, 0.f, 0.f}; a_relu = 0;
-        if (vecA) {
-            const bool second = (a.nsrc == 2 && cg >= a.src[0].C);
-            const SrcDev S = pick_src(a.src[0], a.src[1], second);
-            const int cl = cg - (second ? a.src[0].C : 0);
-            const bool cok = cg < a.Cin;
-            if (cok && S.scale) { asc = *(const f32x4*)(S.scale + cl); ash = *(const f32x4*)(S.shift + cl); }
-            a_relu = S.relu;
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                RowInfo ri = rowinfo[a_r0 + RPP * i];
-                const int ly = (ri.yx >> 16) * a.s_in + dy - S.off_y;
-                const int lx = (ri.yx & 0xffff) * a.s_in + dx - S.off_x;
-                const bool ok = cok && ri.n >= 0 && ly >= 0 && ly < S.LH && lx >= 0 && lx < S.LW;
-                if (ok) {
-                    aok |= 1u << i;
-                    if (POOL) {
-                        const long p = ri.n * S.sN + (long)(2 * ly) * S.sH + (long)(2 * lx) * S.sW + cl;
-                        av[i][0] = ld4t<2>(S.ptr, p);
-                        av[i][1 % NP] = ld4t<2>(S.ptr, p + S.sW);
-                        av[i][2 % NP] = ld4t<2>(S.ptr, p + S.sH);
-                        av[i][3 % NP] = ld4t<2>(S.ptr, p + S.sH + S.sW);
-                    } else {
-                        av[i][0] = ld4t<2>(S.ptr, ri.n * S.sN + (long)ly * S.sH + (long)lx * S.sW + cl);
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                RowInfo ri = rowinfo[a_r0 + RPP * i];
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (ri.n >= 0) {
-                    const int iy = (ri.yx >> 16) * a.s_in + dy, ix = (ri.yx & 0xffff) * a.s_in + dx;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (cg + j < a.Cin) v[j] = load_elem(a.src[0], a.src[1], a.nsrc, ri.n, iy, ix, cg + j);
-                }
-                av[i][0] = v;
-            }
-        }
+        load_a_stage<2, POOL, AR, RPP>(av, asc, ash, a_relu, aok, a, rowinfo, vecA, seg, c0 + 4 * a_c4, a_r0);
         // B tile: packed bf16 weights [slice][K8][Cout][8]
         const elt_t* wb = Wp + ((long)(seg + z) * K8) * a.Cout * 8;
 #pragma unroll
@@ -133,20 +68,7 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const IgemmArgs a, c
     auto write_stage = [&]() {
 #pragma unroll
         for (int i = 0; i < AR; ++i) {
-            f32x4 v = av[i][0];
-            if (vecA) {
-                v = v * asc + ash;
-                if (a_relu) v = relu4(v);
-                if (POOL) {
-#pragma unroll
-                    for (int q = 1; q < NP; ++q) {
-                        f32x4 t = av[i][q] * asc + ash;
-                        if (a_relu) t = relu4(t);
-                        v = max4(v, t);
-                    }
-                }
-                if (!((aok >> i) & 1u)) v = (f32x4){0.f, 0.f, 0.f, 0.f};
-            }
+            const f32x4 v = activate(av[i], asc, ash, a_relu, (aok >> i) & 1u, vecA);
             const int row = a_r0 + RPP * i;
             bf16x4 h;
             h[0] = (elt_t)v[0]; h[1] = (elt_t)v[1]; h[2] = (elt_t)v[2]; h[3] = (elt_t)v[3];
@@ -191,59 +113,7 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const IgemmArgs a, c
         __syncthreads();
     }
 
-    // ---- epilogue (identical to the f32 kernel: f32 outputs, BN-statistics partials) ----
-    const int oyz = z >> 1, oxz = z & 1;
-    const int C1 = a.Cout - a.C0;
-    float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = n0 + wn * 64 + j * 32 + l31;
-        const bool cok = col < a.Cout;
-        const float bias = (a.bias && cok) ? a.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const RowInfo ri = rowinfo[row];
-                if (ri.n >= 0 && cok) {
-                    const bool o32 = a.out_esz == 4;                  // (f32 outputs: the DeepLabV2 classifier maps)
-                    const float v = o32 ? acc[i][j][r] + bias : rndt<2>(acc[i][j][r] + bias);   // statistics see the stored value
-                    const int oy = (ri.yx >> 16) * a.s_out + oyz, ox = (ri.yx & 0xffff) * a.s_out + oxz;
-                    if (col < a.C0) {
-                        const long oi = (((long)ri.n * a.Ho + oy) * a.Wo + ox) * a.C0 + col;
-                        if (o32) st1t<4>(a.out0, oi, v); else st1t<2>(a.out0, oi, v);
-                    } else {
-                        const int y1 = oy - a.o1y, x1 = ox - a.o1x;
-                        if (y1 >= 0 && y1 < a.H1 && x1 >= 0 && x1 < a.W1)
-                            st1t<2>(a.out1, (((long)ri.n * a.H1 + y1) * a.W1 + x1) * C1 + (col - a.C0), v);
-                    }
-                    s1[j] += v; s2[j] += v * v;
-                }
-            }
-        }
-    }
-    if (a.stat) {
-        float* red = (float*)As;   // [WM][2][BN]
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            s1[j] += __shfl_xor(s1[j], 32);
-            s2[j] += __shfl_xor(s2[j], 32);
-            if (lh == 0) {
-                red[(wm * 2 + 0) * BN + wn * 64 + j * 32 + l31] = s1[j];
-                red[(wm * 2 + 1) * BN + wn * 64 + j * 32 + l31] = s2[j];
-            }
-        }
-        __syncthreads();
-        constexpr int HALVES = WM / 2;
-        const int stat_rows = (int)((a.M + 127) / 128);
-        for (int t = tid; t < HALVES * 2 * BN; t += 256) {
-            const int h = t / (2 * BN), q = (t / BN) % 2, c = t % BN;
-            const float v = red[((2 * h) * 2 + q) * BN + c] + red[((2 * h + 1) * 2 + q) * BN + c];
-            const int srow = mtile * HALVES + h;
-            if (srow < stat_rows && n0 + c < a.Cout) a.stat[((long)srow * 2 + q) * a.Cout + n0 + c] = v;
-        }
-    }
+    igemm_epilogue<WM, WN, true>(a, acc, rowinfo, (float*)As, mtile, n0, z, tid);
 }
 
 template <int WM, int WN, bool POOL>
@@ -285,9 +155,8 @@ __global__ void pack_bf16_kernel(const float* __restrict__ w, int Cout, int Cin,
 }  // namespace
 
 int igemm_launch_bf16(const IgemmArgs& a, hipStream_t st) {
-    bool pool = false;
-    for (int i = 0; i < a.nsrc; ++i) pool |= a.src[i].pool != 0;
-    if (a.Cout > 64 || pool) return pool ? launch_cfg<2, 2, true>(a, st) : launch_cfg<2, 2, false>(a, st);
+    const IgemmTile tile = igemm_pick_tile(a);
+    if (tile.wm == 2) return tile.pool ? launch_cfg<2, 2, true>(a, st) : launch_cfg<2, 2, false>(a, st);
     return launch_cfg<4, 1, false>(a, st);
 }
 

@@ -59,15 +59,6 @@ __host__ __device__ __forceinline__ int wrap_add(int x, int inc, int W, float in
     return r;
 }
 
-// XCD-aware block order.  The workgroups of a 1-D grid go round-robin over the 8 XCDs (block bid runs on XCD bid % 8), each with
-// its own L2.  This renumbering -- a permutation of [0, nblk) -- hands every XCD a CONTIGUOUS range of the linear order, so with a
-// (slice-major, tile-minor) order all tiles of one pixel slice run on one XCD: the slice's operands come from HBM once and the
-// other tiles re-read them from that XCD's L2, instead of once per tile spread over all eight.
-__host__ __device__ __forceinline__ int xcd_linear(unsigned bid, int nblk) {
-    const int q = nblk / 8, r = nblk % 8, xcd = bid % 8, jj = bid / 8;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + jj;
-}
-
 // Where a block's next tile lies, for the kernels that walk a range of tiles of a batch cut into tiles_y x tiles_x tiles of TH x TW
 // pixels per image: (image, first row, first column), wave-uniform, stepped without a division.  Tiles of an image are walked
 // DOWN its columns (y fastest): the two dY halo rows a tile shares with the next one are in L2 when that tile asks for them

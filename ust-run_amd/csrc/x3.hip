@@ -19,8 +19,7 @@
 //                     first kernel: a 4 x 16-pixel activation tile against the 6 x 18 dY halo patch, nine accumulators per wave),
 //                     both operands split at staging; one block per CU, 216 MFMAs per wave and tile.
 // Everything else of this dtype (first convolution, ConvTranspose weight gradient, BatchNorm, head, losses) runs the f32 kernels.
-#include "common.h"
-#include "loader.h"
+#include "igemm_tile.h"
 #include "tn_gemm.h"
 #include "x3_split.h"       // split4, mfma6
 #include <type_traits>
@@ -53,7 +52,6 @@ __global__ __launch_bounds__(256) void pack_x3_kernel(const float* __restrict__ 
 // ---- implicit GEMM -----------------------------------------------------------------------------------------------------------
 constexpr int XBK = 32;            // channels per stage
 constexpr int XAP = 80;            // LDS row pitch of an activation plane: 32 bf16 + 16 bytes of padding
-struct RowInfo { int n; int yx; };
 
 template <int WM, int WN>
 __global__ __launch_bounds__(256, 2) void igemm_x3_kernel(const IgemmArgs a, const int mt_total, const int nt_total) {
@@ -64,12 +62,7 @@ __global__ __launch_bounds__(256, 2) void igemm_x3_kernel(const IgemmArgs a, con
     char* As = smem;                                    // [3][BM][XAP]
     RowInfo* rowinfo = (RowInfo*)(smem + 3 * APLANE);
 
-    const int ntiles = mt_total * nt_total;
-    int bid = blockIdx.x;
-    {
-        const int q = ntiles / 8, r = ntiles % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_linear(blockIdx.x, mt_total * nt_total);
     const int mtile = bid / nt_total, ntile = bid % nt_total;
     const int z = blockIdx.y;
     const int n0 = ntile * BN;
@@ -77,19 +70,7 @@ __global__ __launch_bounds__(256, 2) void igemm_x3_kernel(const IgemmArgs a, con
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    for (int r = tid; r < BM; r += 256) {
-        long m = (long)mtile * BM + r;
-        RowInfo ri;
-        if (m < a.M) {
-            int hw = a.Hb * a.Wb;
-            int n = (int)(m / hw);
-            int rem = (int)(m - (long)n * hw);
-            int by = rem / a.Wb;
-            ri.n = n; ri.yx = (by << 16) | (rem - by * a.Wb);
-        } else { ri.n = -1; ri.yx = 0; }
-        rowinfo[r] = ri;
-    }
-    __syncthreads();
+    fill_row_table<BM>(rowinfo, a, mtile, tid);
 
     const int a_c4 = tid & 7, a_r0 = tid >> 3;
     const int nchunk = a.Cin / XBK;
@@ -125,8 +106,8 @@ __global__ __launch_bounds__(256, 2) void igemm_x3_kernel(const IgemmArgs a, con
 #pragma unroll
             for (int i = 0; i < AR; ++i) {
                 const RowInfo ri = rowinfo[a_r0 + 32 * i];
-                const int ly = (ri.yx >> 16) * a.s_in + dy - S.off_y;
-                const int lx = (ri.yx & 0xffff) * a.s_in + dx - S.off_x;
+                const int ly = row_by(ri) * a.s_in + dy - S.off_y;
+                const int lx = row_bx(ri) * a.s_in + dx - S.off_x;
                 const bool ok = ri.n >= 0 && ly >= 0 && ly < S.LH && lx >= 0 && lx < S.LW;
                 aok |= (ok ? 1u : 0u) << i;
                 goff[i] = ok ? ri.n * S.sN + (long)ly * S.sH + (long)lx * S.sW : 0;      // (a clamped address: the value is masked at the split)
@@ -201,57 +182,7 @@ __global__ __launch_bounds__(256, 2) void igemm_x3_kernel(const IgemmArgs a, con
         __syncthreads();
     }
 
-    // ---- epilogue (igemm.hip's): D[row = pixel][col = channel]; col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-    const int oyz = z >> 1, oxz = z & 1;
-    const int C1 = a.Cout - a.C0;
-    float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = n0 + wn * 64 + j * 32 + l31;
-        const bool cok = col < a.Cout;
-        const float bias = (a.bias && cok) ? a.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const RowInfo ri = rowinfo[row];
-                if (ri.n >= 0 && cok) {
-                    const float v = acc[i][j][r] + bias;
-                    const int oy = (ri.yx >> 16) * a.s_out + oyz, ox = (ri.yx & 0xffff) * a.s_out + oxz;
-                    if (col < a.C0) {
-                        a.out0[(((long)ri.n * a.Ho + oy) * a.Wo + ox) * a.C0 + col] = v;
-                    } else {
-                        const int y1 = oy - a.o1y, x1 = ox - a.o1x;
-                        if (y1 >= 0 && y1 < a.H1 && x1 >= 0 && x1 < a.W1)
-                            a.out1[(((long)ri.n * a.H1 + y1) * a.W1 + x1) * C1 + (col - a.C0)] = v;
-                    }
-                    s1[j] += v; s2[j] += v * v;
-                }
-            }
-        }
-    }
-    if (a.stat) {
-        float* red = (float*)As;  // [WM][2][BN], free after the final barrier of the main loop
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            s1[j] += __shfl_xor(s1[j], 32);
-            s2[j] += __shfl_xor(s2[j], 32);
-            if (lh == 0) {
-                red[(wm * 2 + 0) * BN + wn * 64 + j * 32 + l31] = s1[j];
-                red[(wm * 2 + 1) * BN + wn * 64 + j * 32 + l31] = s2[j];
-            }
-        }
-        __syncthreads();
-        constexpr int HALVES = WM / 2;     // one statistics row per 128 pixels (ustrun_conv_mtiles)
-        const int stat_rows = (int)((a.M + 127) / 128);
-        for (int t = tid; t < HALVES * 2 * BN; t += 256) {
-            const int h = t / (2 * BN), q = (t / BN) % 2, c = t % BN;
-            const float v = red[((2 * h) * 2 + q) * BN + c] + red[((2 * h + 1) * 2 + q) * BN + c];
-            const int srow = mtile * HALVES + h;
-            if (srow < stat_rows && n0 + c < a.Cout) a.stat[((long)srow * 2 + q) * a.Cout + n0 + c] = v;
-        }
-    }
+    igemm_epilogue<WM, WN, false>(a, acc, rowinfo, (float*)As, mtile, n0, z, tid);
 }
 
 // ---- 3x3 convolution, halo-tiled -------------------------------------------------------------------------------------------
@@ -271,12 +202,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_x3_kernel(const IgemmArgs a, c
     constexpr int BN = 64 * WN;
     extern __shared__ __attribute__((aligned(16))) char smem[];     // [3][180 px][XAP]
     const int mt_total = a.N * tiles_y * tiles_x;
-    const int ntiles = mt_total * nt_total;
-    int bid = blockIdx.x;
-    {
-        const int q = ntiles / 8, r = ntiles % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_linear(blockIdx.x, mt_total * nt_total);
     const int mtile = bid / nt_total, ntile = bid % nt_total;
     const int img = mtile / (tiles_y * tiles_x), trem = mtile - img * tiles_y * tiles_x;
     const int y0 = (trem / tiles_x) * CTH, x0 = (trem % tiles_x) * CTW;
