@@ -122,7 +122,7 @@ CASES = [
     # image row) of 9 steps (the last one 6 rows) in three passes, 10 steps per block
     ("ws64f_130_64", 130, (64,), 64, 64, 64, 2, "wsf", "wsf"),
     ("ws64f_ragged", 90, (64,), 64, 70, 80, 3, "wsf", "wsf"),
-    # ---- what the padding-aware tile rule (conv_halo_bf16.hip::halo_tile128, round 3) selects on the maps of BASELINE.json
+    # ---- what the padding-aware tile rule (halo_plan.h::halo_tile128, round 3) selects on the maps of BASELINE.json
     # configs[2] / configs[3] (prostate 384 x 384: 48 / 24-pixel levels; M&Ms 288 x 288: 144 / 18-pixel levels;
     # reference train.py:416-418, train_mnms.py:397-399) -- VERDICT r3 next 3.  48 x 48 is >= 32 wide but pads 48 -> 64 on
     # the 8 x 32 tile: the rule takes 16 x 16 tiles; 18 x 18 and 24 x 24 pad to 32 on 16 x 16 tiles: 8 x 16 MI 2;

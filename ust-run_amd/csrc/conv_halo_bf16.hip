@@ -11,13 +11,12 @@
 // 64 with 2x2 accumulators, MI = 2, for small grids and 64-channel outputs).  Two blocks per CU.
 #include "common.h"
 #include "loader.h"
+#include "halo_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace ustrun {
 namespace {
-
-
 
 __device__ __attribute__((aligned(16))) const unsigned g_zero16[4] = {0u, 0u, 0u, 0u};   // source of padding pixels
 
@@ -74,39 +73,11 @@ template <int TH, int TW, int BN, int BK, int MI, bool POOL, int NT, bool XF, in
           int LINW = 0>
 __global__ __launch_bounds__(256, (TH * TW * BN >= 512 * 64 && BN == 64 ? 1 : 2)) void conv3x3_halo_bf16_kernel(const IgemmArgs a, const int tiles_x, const int tiles_y,
                                                                    const int nt_total) {
-    static_assert(BK == 32, "80-byte patch rows hold one 32-channel chunk");
-    constexpr bool LIN = LINW > 0;
-    constexpr int RP = LINW + 1;                // LIN: row pitch of the flat padded space
-    constexpr int TM = TH * TW;
-    static_assert(!LIN || (DIL == 1 && !POOL && TW == 32 && BREG && RP > 8), "linear tiles: un-dilated, un-pooled, 32-position sub-tiles");
-    static_assert(!M16 || (BREG && !XF), "the 16x16x32 build: plain sources, weights through registers");
-    static_assert(!BNS || M16, "BatchNorm-backward sums ride on the 16x16x32 epilogue (8 channels of a pixel per lane)");
-    static_assert(!BREG || NT <= 2, "register-fed weights: 16 registers per tap and set");
-    constexpr int HW2 = LIN ? RP : TW + 2 * DIL;
-    constexpr int SR = 32 / TW;                 // tile rows per 32-pixel sub-tile (2 or 1)
-    constexpr int WM = TH / (SR * MI), WN = 4 / WM;
-    static_assert(WM * WN == 4 && BN == WN * 64, "4 waves, 64 channels per wave");
-    constexpr int HP = LIN ? TM + 2 * RP + 2 : (TH + 2 * DIL) * HW2;    // halo pixels
-    constexpr int PITCH = 80;                   // patch row: 4 x 16 B of channels + 16 B pad
-    constexpr int DSLOTS = (HP * 5 + 63) / 64 * 64;   // direct staging: 16-byte LDS slots incl. the pad slots, whole waves
-    constexpr int XSLOTS = (HP * 4 + 63) / 64 * 64;   // transform staging: (pixel, channel group) items, whole waves
-    constexpr int AIT = (DSLOTS + 255) / 256;   // staging steps per chunk (taps 0 .. AIT-1), one item per thread each
-    constexpr int NSTG = (9 + NT - 1) / NT;     // stages per chunk: NT taps (weight tiles) per barrier
-    constexpr int BATCH = (AIT + NSTG - 2) / (NSTG - 1);   // patch items per stage; the chunk's last stage carries the constants
-    static_assert(BATCH * (NSTG - 1) >= AIT, "staging fits the chunk");
-    constexpr int NP = POOL ? 4 : 1;
-    // BREG: every wave issues every staging step (its transfer counts are then compile-time constants, see the counted wait):
-    // the slots past the patch image are a few hundred bytes of trash behind it
-    constexpr int ABYTES = (BREG ? AIT * 256 : DSLOTS) * 16;
-    constexpr int BCH = (BK / 8) * BN;          // 16-byte chunks per B tile
-    constexpr int BIT = BCH / 256;
-    static_assert(BCH % 256 == 0, "B tile must be a whole number of wave-instructions per wave");
-    constexpr int RAWB = XF ? BATCH * NP * 4096 : 0;   // a raw slot: BATCH x NP x 16 B per thread
-    // SKEW: the items a stage fetches are transformed under the NEXT stage's MFMAs (two raw slots, by stage parity) --
-    // where a second slot still leaves room for two blocks per CU; otherwise after the stage's own MFMAs
-    constexpr int BBYTES = BREG ? 0 : 2 * NT * BCH * 16;
-    constexpr bool SKEW = XF && 2 * ABYTES + BBYTES + 2 * RAWB + 512 <= 81920;
-    constexpr int NRAW = SKEW ? 2 : 1;
+    using G = HaloGeom<TH, TW, BN, BK, MI, POOL, NT, XF, DIL, BREG, M16, BNS, LINW>;      // halo_plan.h: the launch sizes LDS from the same struct
+    constexpr bool LIN = G::LIN, SKEW = G::SKEW;
+    constexpr int RP = G::RP, TM = G::TM, HW2 = G::HW2, SR = G::SR, WM = G::WM, WN = G::WN, HP = G::HP, PITCH = G::PITCH;
+    constexpr int DSLOTS = G::DSLOTS, XSLOTS = G::XSLOTS, AIT = G::AIT, NSTG = G::NSTG, BATCH = G::BATCH, NP = G::NP;
+    constexpr int ABYTES = G::ABYTES, BCH = G::BCH, BIT = G::BIT, RAWB = G::RAWB, BBYTES = G::BBYTES, NRAW = G::NRAW;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* As = smem;                            // 2 x patch [HP][80 B] (current / being staged)
@@ -859,264 +830,51 @@ __global__ __launch_bounds__(256, (TH * TW * BN >= 512 * 64 && BN == 64 ? 1 : 2)
     }
 }
 
-thread_local int g_last_variant = 0;    // (per calling thread) TH<<24 | TW<<16 | BN<<8 | MI<<4 | NT<<2 | POOL<<1 | XF of the last launch (tests: ustrun_debug_last_conv_variant)
-                                        // (linear tiles: bit 30 | W << 16 | ...)
+thread_local int g_last_variant = 0;    // (per calling thread) halo_variant() of the last launch (tests: ustrun_debug_last_conv_variant)
 
-// linear tiles (LINW): passes and tiles of a launch.  A pass = the images that share BatchNorm constants (the sources' gN, or the
-// gN of the BatchNorm-backward sums the launch forms; the whole batch without either); tiles never cross one.
-struct LinPlan { int gN, tpp, mtiles, last_rows; };
-static LinPlan lin_plan(const IgemmArgs& a) {
-    int g = a.pass_gN > 0 ? a.pass_gN : 0;
-    for (int i = 0; i < a.nsrc && !g; ++i)
-        if (a.src[i].gN > 0) g = a.src[i].gN;
-    if (!g && a.bn_gN > 0) g = a.bn_gN;
-    if (g <= 0 || g > a.N) g = a.N;
-    const long IS = (long)(a.Ho + 1) * (a.Wo + 1);
-    const int tpp = (int)cdiv(g * IS, 256L), full = a.N / g, tailN = a.N - full * g, tail = (int)cdiv(tailN * IS, 256L);
-    return {g, tpp, full * tpp + tail, tailN ? tail : (full > 1 ? tpp : -1)};
-}
-
-template <int TH, int TW, int BN, int BK, int MI, bool POOL, int NT, bool XF, int DIL = 1, bool BREG = false, bool M16 = false, bool BNS = false,
-          int LINW = 0>
-int launch_xf(const IgemmArgs& a, hipStream_t st) {
-    g_last_variant = (LINW ? (1 << 30 | LINW << 16) : (TH << 24 | TW << 16)) | BN << 8 | (M16 ? 0x80 : 0) | MI << 4 | NT << 2 | (POOL ? 2 : 0) | (XF ? 1 : 0);
-    const LinPlan lp = LINW ? lin_plan(a) : LinPlan{0, 0, 0, -1};
-    const int tx = LINW ? lp.tpp : cdiv(a.Wb, TW), ty = LINW ? lp.gN : cdiv(a.Hb, TH), nt = a.Cout / BN;
-    constexpr int DSLOTS = ((LINW ? TH * TW + 2 * (LINW + 1) + 2 : (TH + 2 * DIL) * (TW + 2 * DIL)) * 5 + 63) / 64 * 64;
-    constexpr int AIT = (DSLOTS + 255) / 256, NSTG = (9 + NT - 1) / NT, BATCH = (AIT + NSTG - 2) / (NSTG - 1);
-    const size_t rawb = XF ? (size_t)BATCH * (POOL ? 4 : 1) * 4096 : 0;
-    const size_t fixed = 2 * (size_t)(BREG ? AIT * 256 : DSLOTS) * 16 + (BREG ? 0 : 2 * NT * (size_t)(BK / 8) * BN * 16) + 512;
-    const size_t lds = fixed + (XF && fixed + 2 * rawb <= 81920 ? 2 : 1) * rawb;
-    dim3 grid((LINW ? lp.mtiles : a.N * ty * tx) * nt), block(256);
+template <int TH, int TW, int BN, int BK, int MI, bool POOL, int NT, bool XF, int DIL, bool BREG, bool M16, bool BNS, int LINW>
+int launch_xf(const IgemmArgs& a, const HaloPlan& p, hipStream_t st) {
+    constexpr int lds = HaloGeom<TH, TW, BN, BK, MI, POOL, NT, XF, DIL, BREG, M16, BNS, LINW>::lds;
+    dim3 grid(p.mtiles * p.ntiles), block(256);
     // above the 64 KB default (the dilation-4 patch pair: 93 KB; the 16 x 16 x 128 transforming tile: 66 KB): raise the limit
     // whatever the dilation is (the un-dilated 16 x 16 tile used to launch without the attribute)
     if (lds > 64 * 1024)
-        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_halo_bf16_kernel<TH, TW, BN, BK, MI, POOL, NT, XF, DIL, BREG, M16, BNS, LINW>, (int)lds, "conv3x3_halo_bf16"));
-    hipLaunchKernelGGL((conv3x3_halo_bf16_kernel<TH, TW, BN, BK, MI, POOL, NT, XF, DIL, BREG, M16, BNS, LINW>), grid, block, lds, st, a, tx, ty, nt);
+        USTRUN_TRY(ensure_dynamic_lds((const void*)conv3x3_halo_bf16_kernel<TH, TW, BN, BK, MI, POOL, NT, XF, DIL, BREG, M16, BNS, LINW>, lds, "conv3x3_halo_bf16"));
+    hipLaunchKernelGGL((conv3x3_halo_bf16_kernel<TH, TW, BN, BK, MI, POOL, NT, XF, DIL, BREG, M16, BNS, LINW>), grid, block, lds, st, a, p.tiles_x, p.tiles_y, p.ntiles);
     USTRUN_LAUNCH_CHECK("conv3x3_halo_bf16");
     return 0;
 }
 
-// XF: some source needs arithmetic on load (BatchNorm affine, ReLU, pooling); plain sources (dY, ConvTranspose outputs)
-// then pass through the same path with scale 1, shift 0, floor -inf
-template <int TH, int TW, int BN, int BK, int MI, bool POOL, int NT = 1>
-int launch_cfg(const IgemmArgs& a, hipStream_t st) {
-    bool xf = POOL;
-    for (int i = 0; i < a.nsrc; ++i) xf |= a.src[i].scale != nullptr || a.src[i].relu != 0;
-    if constexpr (POOL) return launch_xf<TH, TW, BN, BK, MI, POOL, NT, true>(a, st);
-    else {
-        {                                              // weights through registers, one barrier per chunk (debug flag bit 3: off)
-            // the 16x16x32 build (round 4): measured ahead on the input gradients of every layer (profiles/r04_ab_halo_m16.log:
-            // 512 -> 512 at 32 x 32 0.220 -> 0.202 ms, 1024 -> 1024 0.217 -> 0.201, 128 -> 128 -1.5 %): the default for plain
-            // sources on the 256-pixel tiles.  ustrun_debug_flags bit 15 (32768): every plain-source tile on it (A/B runs of
-            // the smaller tiles); bit 21 (2097152): none.
-            {
-                const bool m16 = !(g_debug_flags & 8) && !(g_debug_flags & 2097152) && ((g_debug_flags & 32768) || (!xf && MI == 4 && NT == 1));
-                if constexpr (MI == 4 && NT == 1 && BN == 128) {      // (halo_bnsum_supported admits these two tiles only)
-                    if (a.bny) {
-                        USTRUN_CHECK(m16 && !xf && a.stat && a.bnsc && a.bnsh, "conv3x3_halo: BatchNorm-backward sums need a plain source on the 16x16x32 build");
-                        return launch_xf<TH, TW, BN, BK, MI, POOL, NT, false, 1, true, true, true>(a, st);
-                    }
-                }
-                if (m16 && !xf)      // (the transforming variants on it sit 160 registers past the file: not built)
-                    return launch_xf<TH, TW, BN, BK, MI, POOL, NT, false, 1, true, true>(a, st);
-            }
-            if (!(g_debug_flags & 8))
-                return xf ? launch_xf<TH, TW, BN, BK, MI, POOL, NT, true, 1, true>(a, st) : launch_xf<TH, TW, BN, BK, MI, POOL, NT, false, 1, true>(a, st);
-        }
-        return xf ? launch_xf<TH, TW, BN, BK, MI, POOL, NT, true>(a, st) : launch_xf<TH, TW, BN, BK, MI, POOL, NT, false>(a, st);
-    }
-}
+// every kernel of the list, selected by a plan or not, in the list's order (= their order in the code object)
+#define HALO_KERNEL(TH, TW, BN, MI, POOL, NT, XF, DIL, BREG, M16, BNS, LINW) \
+    template __global__ void conv3x3_halo_bf16_kernel<TH, TW, BN, 32, MI, POOL, NT, XF, DIL, BREG, M16, BNS, LINW>(const IgemmArgs, const int, const int, const int);
+HALO_BUILDS(HALO_KERNEL, HALO_KERNEL)
+#undef HALO_KERNEL
 
 }  // namespace
 
 int halo_last_variant() { return g_last_variant; }
-static int halo_dilation(const IgemmArgs& a) { return a.dstep < 0 ? -a.dstep : a.dstep; }
 void set_last_variant(int v) { g_last_variant = v; }
 
-// stat rows the halo kernel writes for an N x H x W output (one per 8 x 16 pixels)
-int halo_stat_rows(int N, int H, int W) { return N * cdiv(H, 8) * cdiv(W, 16); }
-
-// can this conv3x3-shaped problem run on the halo kernel?
-bool halo_supported(const IgemmArgs& a) {
-    if (a.nseg != 9 || a.nz != 1 || a.s_in != 1 || a.s_out != 1 || a.segw != 3) return false;
-    const int dil = a.dstep < 0 ? -a.dstep : a.dstep;
-    if (a.d0 != -a.dstep || !(dil == 1 || dil == 2 || dil == 4)) return false;      // (other rates: the generic kernel)
-    bool pool = false;
-    if (a.out_esz != 2 || (a.C0 & 7) || ((a.Cout - a.C0) & 7) || a.bias) return false;     // (3x3 convs here carry no bias)
-    for (int i = 0; i < a.nsrc; ++i) {
-        if (a.src[i].sC != 1 || (a.src[i].C & 7) || a.src[i].esz != 2) return false;
-        pool |= a.src[i].pool != 0;
-    }
-    const int BK = 32;
-    if (a.Cin % BK || a.Cout % 64) return false;
-    if (a.nsrc == 2 && (a.src[0].C % BK)) return false;
-    if (pool && (a.nsrc != 1 || a.Cout % 128)) return false;
-    if (a.Hb < 4 || a.Wb < 8) return false;      // tiny extents: the generic kernel wastes less
-    if (dil > 1 && (pool || a.nsrc != 1)) return false;
-    return true;
-}
-
-int halo_tile128(const IgemmArgs& a);
-static double halo_rect_score(const IgemmArgs& a);
-
-// Linear tiles (LINW builds: 18, 24, 36, 72-pixel rows): the row length if this launch runs on them, else 0.  They serve
-// 128-column outputs of un-pooled, un-dilated sources when (a) the rectangular tiles would waste more of their MFMAs on padding --
-// useful fraction x the tiles' measured relative rates, as in halo_tile128 -- and (b) the launch still has a block per CU.
-// (ustrun_debug_flags2 bit 0: off, for A/B runs)
-int halo_linear_w(const IgemmArgs& a) {
-    if ((g_debug_flags2 & 1) || (g_debug_flags & (8 | 2097152 | 32768)) || ((g_debug_flags >> 10) & 3)) return 0;
-    if (!halo_supported(a) || halo_dilation(a) != 1 || a.Cout % 128 || a.Hb != a.Ho || a.Wb != a.Wo) return 0;
-    const int w = a.Wo;
-    if (!(w == 18 || w == 24 || w == 36 || w == 72)) return 0;
-    int g = a.pass_gN > 0 ? a.pass_gN : 0;
-    for (int i = 0; i < a.nsrc; ++i) {
-        if (a.src[i].pool) return 0;
-        if (a.src[i].gN > 0) { if (g && g != a.src[i].gN) return 0; g = a.src[i].gN; }
-    }
-    if (a.bny && a.bn_gN > 0 && g && g != a.bn_gN) return 0;
-    const LinPlan lp = lin_plan(a);
-    for (int i = 0; i < a.nsrc; ++i)
-        if ((long)lp.gN * a.src[i].sN * 2 >= (1L << 31) - 4096) return 0;          // 32-bit byte offsets inside a pass
-    if ((long)lp.mtiles * (a.Cout / 128) < 160) return 0;
-    const double lin = (double)a.N * a.Ho * a.Wo / (lp.mtiles * 256.0);
-    return lin > 1.05 * halo_rect_score(a) ? w : 0;
-}
-// statistics rows of the last pass of a linear-tile launch (-1: not one, or a single pass)
-int halo_linear_last_pass_rows(const IgemmArgs& a) { return halo_linear_w(a) ? lin_plan(a).last_rows : -1; }
-
-// can this input-gradient launch also form the BatchNorm-backward sums of the layer whose da it writes?  (one plain source, one
-// destination, the two 256-pixel x 128-channel tiles on the 16x16x32 build)
-bool halo_bnsum_supported(const IgemmArgs& a) {
-    if (!halo_supported(a) || a.nsrc != 1 || a.out1 || a.C0 != a.Cout || a.Cout % 128) return false;
-    if (a.src[0].scale || a.src[0].relu || a.src[0].pool) return false;
-    if ((g_debug_flags & (8 | 2097152))) return false;
-    if (halo_dilation(a) != 1) return a.bn_gN == 0;      // (round 6) the dilated tiles of DeepLabV2-ResNet: launch_dilated's 16x16x32 builds
-    if (halo_linear_w(a)) return true;
-    const int t = halo_tile128(a);
-    return t == 0 || t == 1;
-}
-
-// 16-row tiles (256 px x 128 ch per block) read fewer LDS/weight bytes per flop but need >= 2 blocks per CU
-bool halo_tall_tile(const IgemmArgs& a) {
-    return (long)a.N * cdiv(a.Hb, 16) * cdiv(a.Wb, 16) * (a.Cout / 128) >= 512;
-}
-
-// Tile of the 128-column, un-pooled, un-dilated case: 0 = 8 x 32 px (MI 4), 1 = 16 x 16 px (MI 4), 2 = 8 x 16 px (MI 2, 128 columns),
-// 3 = 8 x 16 px, 64 columns (less than one block per CU).  ustrun_debug_flags bits 10-11 force 0..2 (+1) for A/B runs.
-// useful MFMA fraction x relative rate of the rectangular tile conv3x3_halo_launch_bf16 would pick (128-column, un-pooled case)
-static double halo_rect_score(const IgemmArgs& a) {
-    const double h8 = cdiv(a.Hb, 8) * 8.0, h16 = cdiv(a.Hb, 16) * 16.0, w16 = cdiv(a.Wb, 16) * 16.0, w32 = cdiv(a.Wb, 32) * 32.0;
-    const double hw = (double)a.Hb * a.Wb;
-    switch (halo_tile128(a)) {
-        case 0: return hw / (h8 * w32);
-        case 1: return 0.93 * hw / (h16 * w16);
-        default: return 0.80 * hw / (h8 * w16);
-    }
-}
-
-int halo_tile128(const IgemmArgs& a) {
-    const int force = (g_debug_flags >> 10) & 3;
-    const bool wide = a.Wb >= 32;
-    if (force) return (force == 1 && !wide) ? 1 : force - 1;
-    if (halo_tall_tile(a)) {
-        // enough blocks for any tile: the one that wastes the fewest MFMAs on padding, weighted by the tiles' measured relative
-        // rates on full tiles (8 x 32: 1, 16 x 16: 0.93, 8 x 16 with two sub-tiles per wave: 0.80 -- profiles/r03_ab_halo_tiles.log:
-        // 512 -> 512 at 48 x 48: 0.346 -> 0.290 ms on 16 x 16 tiles; 1024 -> 1024 at 18 x 18 and 24 x 24: -9 % on 8 x 16).  Maps
-        // whose sides are multiples of 32 (every level of the 256 x 256 workloads) keep the 8 x 32 tile.
-        const double h8 = cdiv(a.Hb, 8) * 8.0, h16 = cdiv(a.Hb, 16) * 16.0, w16 = cdiv(a.Wb, 16) * 16.0, w32 = cdiv(a.Wb, 32) * 32.0;
-        const double s0 = wide ? 1.0 / (h8 * w32) : 0.0, s1 = 0.93 / (h16 * w16), s2 = 0.80 / (h8 * w16);
-        return (s0 >= s1 && s0 >= s2) ? 0 : (s1 >= s2 ? 1 : 2);
-    }
-    if ((long)a.N * cdiv(a.Hb, 8) * cdiv(a.Wb, 16) * (a.Cout / 128) < 256) return 3;      // less than one block per CU
-    return 2;
-}
-
-// BatchNorm-statistics rows written by the configuration conv3x3_halo_launch_bf16 picks
-int halo_stat_rows_used(const IgemmArgs& a) {
-    if (halo_linear_w(a)) return lin_plan(a).mtiles;          // one row per 256-position tile
-    if (halo_dilation(a) == 4 && a.Cout % 128 == 0) return a.N * cdiv(a.Hb, 16) * 2 * cdiv(a.Wb, 16);       // 16 x 16 tiles, two rows each
-    if (halo_dilation(a) > 1) return a.N * cdiv(a.Hb, 8) * cdiv(a.Wb, 16);
-    bool pool = false;
-    for (int i = 0; i < a.nsrc; ++i) pool |= a.src[i].pool != 0;
-    const bool wide = a.Wb >= 32;
-    if (pool) return a.N * cdiv(a.Hb, 8) * cdiv(a.Wb, 16);
-    if (a.Cout % 128 == 0) {
-        const int t = halo_tile128(a);
-        return t == 0 ? a.N * cdiv(a.Hb, 8) * cdiv(a.Wb, 32) : t == 1 ? a.N * cdiv(a.Hb, 16) * 2 * cdiv(a.Wb, 16) : a.N * cdiv(a.Hb, 8) * cdiv(a.Wb, 16);
-    }
-    if (wide && (g_debug_flags & 8192) && a.Hb >= 16) return a.N * cdiv(a.Hb, 16) * 2 * cdiv(a.Wb, 32);
-    return wide ? a.N * cdiv(a.Hb, 8) * cdiv(a.Wb, 32) : a.N * cdiv(a.Hb, 16) * 2 * cdiv(a.Wb, 16);
-}
-
-// dilated 3x3 (DeepLabV2-ResNet layer3 / layer4): 8 x 16-pixel tiles keep the (8 + 2d) x (16 + 2d) patch pair small at rate 2
-template <int DIL>
-static int launch_dilated(const IgemmArgs& a, hipStream_t st) {
-    bool xf = false;
-    for (int i = 0; i < a.nsrc; ++i) xf |= a.src[i].scale != nullptr || a.src[i].relu != 0;
-    const bool breg = !(g_debug_flags & 8);          // weights through registers, one barrier per chunk (round 3)
-    if (a.bny) {        // input gradient + BatchNorm-backward sums (halo_bnsum_supported): the 16x16x32 build of the rate's tile
-        USTRUN_CHECK(breg && !xf && a.stat && a.bnsc && a.bnsh && a.Cout % 128 == 0, "conv3x3_halo: BatchNorm-backward sums need a plain source on the 16x16x32 build");
-        if (DIL == 4) return launch_xf<16, 16, 128, 32, 4, false, 1, false, DIL, true, true, true>(a, st);
-        return launch_xf<8, 16, 128, 32, 2, false, 2, false, DIL, true, true, true>(a, st);
-    }
-    if (a.Cout % 128 == 0) {
-        // rate 4: the (8 + 8) x (16 + 8) patch of an 8 x 16 tile is three times its output and its pair of buffers leaves room
-        // for ONE block per CU anyway -- a 16 x 16 tile (24 x 24 patch: 2.25 x) with the 4 x 2 wave tile does twice the MFMA
-        // work per stage in that one block: 0.49 -> 0.39 ms on layer4's 512 -> 512 convolutions (627 -> 786 TF/s).  Rate 2
-        // keeps the small tile (two blocks per CU; the large one measured 0.089 -> 0.108 ms there).
-        if (DIL == 4) {
-            if (breg) return xf ? launch_xf<16, 16, 128, 32, 4, false, 1, true, DIL, true>(a, st) : launch_xf<16, 16, 128, 32, 4, false, 1, false, DIL, true>(a, st);
-            return xf ? launch_xf<16, 16, 128, 32, 4, false, 1, true, DIL>(a, st) : launch_xf<16, 16, 128, 32, 4, false, 1, false, DIL>(a, st);
-        }
-        if (breg) return xf ? launch_xf<8, 16, 128, 32, 2, false, 2, true, DIL, true>(a, st) : launch_xf<8, 16, 128, 32, 2, false, 2, false, DIL, true>(a, st);
-        return xf ? launch_xf<8, 16, 128, 32, 2, false, 2, true, DIL>(a, st) : launch_xf<8, 16, 128, 32, 2, false, 2, false, DIL>(a, st);
-    }
-    if (breg) return xf ? launch_xf<8, 16, 64, 32, 1, false, 2, true, DIL, true>(a, st) : launch_xf<8, 16, 64, 32, 1, false, 2, false, DIL, true>(a, st);
-    return xf ? launch_xf<8, 16, 64, 32, 1, false, 2, true, DIL>(a, st) : launch_xf<8, 16, 64, 32, 1, false, 2, false, DIL>(a, st);
-}
-
-template <int W>
-static int launch_linear(const IgemmArgs& a, hipStream_t st) {
-    bool xf = false;
-    for (int i = 0; i < a.nsrc; ++i) xf |= a.src[i].scale != nullptr || a.src[i].relu != 0;
-    if (a.bny) {
-        USTRUN_CHECK(!xf && a.stat && a.bnsc && a.bnsh, "conv3x3_halo: BatchNorm-backward sums need a plain source");
-        return launch_xf<8, 32, 128, 32, 4, false, 1, false, 1, true, true, true, W>(a, st);
-    }
-    return xf ? launch_xf<8, 32, 128, 32, 4, false, 1, true, 1, true, false, false, W>(a, st)
-              : launch_xf<8, 32, 128, 32, 4, false, 1, false, 1, true, true, false, W>(a, st);
-}
+// every question about a launch is a read of its plan (halo_plan.h), under the calling thread's debug flags
+static HaloPlan plan_of(const IgemmArgs& a) { return halo_plan(a, g_debug_flags, g_debug_flags2); }
+bool halo_supported(const IgemmArgs& a) { return halo_plan_supported(a); }
+int halo_stat_rows_used(const IgemmArgs& a) { return plan_of(a).stat_rows; }
+int halo_linear_last_pass_rows(const IgemmArgs& a) { return plan_of(a).last_rows; }
+bool halo_bnsum_supported(const IgemmArgs& a) { return plan_of(a).bns_ok; }
 
 int conv3x3_halo_launch_bf16(const IgemmArgs& a, hipStream_t st) {
-    if (halo_dilation(a) == 2) return launch_dilated<2>(a, st);
-    if (halo_dilation(a) == 4) return launch_dilated<4>(a, st);
-    switch (halo_linear_w(a)) {
-        case 18: return launch_linear<18>(a, st);
-        case 24: return launch_linear<24>(a, st);
-        case 36: return launch_linear<36>(a, st);
-        case 72: return launch_linear<72>(a, st);
-        default: break;
+    const HaloPlan p = plan_of(a);
+    USTRUN_CHECK(p.ok, "conv3x3_halo: not a launch of this kernel");
+    USTRUN_CHECK(!a.bny || (p.bns && a.stat && a.bnsc && a.bnsh), "conv3x3_halo: BatchNorm-backward sums need a plain source on the 16x16x32 build");
+    g_last_variant = p.variant;
+    switch (p.key) {
+#define HALO_CASE(TH, TW, BN, MI, POOL, NT, XF, DIL, BREG, M16, BNS, LINW) \
+    case halo_key(TH, TW, BN, MI, POOL, NT, XF, DIL, BREG, M16, BNS, LINW): return launch_xf<TH, TW, BN, 32, MI, POOL, NT, XF, DIL, BREG, M16, BNS, LINW>(a, p, st);
+        HALO_BUILDS(HALO_CASE, HALO_NONE)
+#undef HALO_CASE
     }
-    bool pool = false;
-    for (int i = 0; i < a.nsrc; ++i) pool |= a.src[i].pool != 0;
-    const bool wide = a.Wb >= 32;                 // 32-pixel rows: conflict-free A fragment reads
-    // MI = 2 tiles run two taps per barrier (16 MFMAs per wave and stage, like the MI = 4 tiles)
-    if (pool) return launch_cfg<8, 16, 128, 32, 2, true, 2>(a, st);
-    if (a.Cout % 128 == 0) {
-        // 256 px x 128 ch per block, wave tile 128 px x 64 ch (tiles 0, 1); less than one block per CU (the batch-1 forward,
-        // validation at test_bs 1): twice the blocks at 64 channels each (tile 3: 20-25 % faster per layer at batch 1)
-        switch (halo_tile128(a)) {
-            case 0: return launch_cfg<8, 32, 128, 32, 4, false>(a, st);
-            case 1: return launch_cfg<16, 16, 128, 32, 4, false>(a, st);
-            case 3: return launch_cfg<8, 16, 64, 32, 1, false, 2>(a, st);
-            default: return launch_cfg<8, 16, 128, 32, 2, false, 2>(a, st);
-        }
-    }
-    // (ustrun_debug_flags bit 13 = 8192: the 512-pixel x 64-channel tile, wave tile 128 px x 64 ch, one block per CU -- A/B runs)
-    if (wide && (g_debug_flags & 8192) && a.Hb >= 16) return launch_cfg<16, 32, 64, 32, 4, false, 1>(a, st);
-    if (wide) return launch_cfg<8, 32, 64, 32, 2, false, 2>(a, st);
-    return launch_cfg<16, 16, 64, 32, 2, false, 2>(a, st);
+    USTRUN_CHECK(false, "conv3x3_halo: no build for plan %#x (dilation %d, register-fed weights %d, sums %d)", p.variant, p.dil, (int)p.breg, (int)p.bns);
 }
 
 }  // namespace ustrun
