@@ -130,6 +130,13 @@ int ustrun_convT2x2_fwd(const ustrun_src_t* src, const void* w_fwd, const float*
 int ustrun_conv_first_dgrad(const void* dy, const float* w, int N, int H, int W, int Cout, int Cin, float* dx,
                             int dtype, ustrun_stream_t s);
 
+/* ---- input gradient of the ResNet stem (Conv2d(3, 64, 7, stride=2, padding=3, bias=False), resnet.py:124,160) ----
+ * dx[N,Cin,H,W] NCHW f32 (overwritten) from dy[N,Ho,Wo,Cout] in the storage dtype, Ho = (H-1)/2+1, Wo = (W-1)/2+1, and
+ * the f32 PARAMETER w[Cout,Cin,7,7] (no pack).  Cin 3, Cout a multiple of 8 up to 64, any H, W >= 1.  Products of the
+ * stored values, f32 accumulation in a fixed order (bit-identical repeats); USTRUN_F32X3 runs the f32 build.           */
+int ustrun_conv_stem_dgrad(const void* dy, const float* w, int N, int H, int W, int Cout, int Cin, float* dx,
+                           int dtype, ustrun_stream_t s);
+
 /* ---- 1x1 head with bias: replaces OutConv, unet_parts.py:71-76 -----------------------------
  * logits NCHW f32 [N,K,H,W] from y[N,H,W,C] through the loader affine (scale/shift/relu).    */
 int ustrun_head_fwd(const void* y, const float* scale, const float* shift, int64_t npix, int HW,

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """GPU box: forward throughput of DeepLabV2-ResNet101 at BASELINE.json configs[4]'s shape (BUSI 512x512, 2 classes) through
 libustrun.so -- images/s, achieved TFLOP/s of the convolution launches (HIP-event pairs, algorithmic flops) and the share of
-time by kernel class; --backward times forward + backward (every parameter's gradient, ustrun.resnet_engine.DeepLabFn).
+time by kernel class; --backward times forward + backward (every parameter's gradient, ustrun.resnet_engine.DeepLabFn);
+--input_grad 1 (with --backward) then times the same step with x.requires_grad (x.grad through ustrun_conv_stem_dgrad) beside it.
 
     python tools/bench_deeplab.py [--n 16] [--hw 512] [--dtype bf16] [--mode train|eval] [--reps 5] [--arch resnet101] [--backward]
+                                  [--input_grad 1]
 """
 import argparse
 import ctypes
@@ -26,6 +28,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--arch", default="resnet101")
     ap.add_argument("--backward", action="store_true")
+    ap.add_argument("--input_grad", type=int, default=0, help="1 (with --backward): also forward + backward with x.requires_grad")
     ap.add_argument("--ssl", action="store_true", help="the whole semi-supervised step (ustrun.trainer.SSLTrainer) around the model: "
                     "BUSI shapes, label_bs = unlabel_bs = --n")
     a = ap.parse_args()
@@ -170,8 +173,64 @@ def bench_backward(a, m, x, lib, _lib):
     print(f"DeepLabV2-{a.arch} train-mode forward + backward, N={a.n} {a.hw}x{a.hw}, {a.dtype}: {dt * 1e3:.2f} ms = {a.n / dt:.1f} images/s; "
           + "; ".join(out) + f"; peak device memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
     ph = phase_times(step)
+    if a.input_grad:
+        input_grad_beside(a, m, x, dl, step)
     print("   stream time by engine helper (ms; bottleneck = the whole forward block, conv_bn inside it; _conv_dgrad includes _zero_insert; _conv3_dgrad_bn2 / _conv1_dgrad_join include their _bn_apply / _finalize_fused_sums / fallbacks): "
           + ", ".join(f"{k} {v:.2f}" for k, v in ph.items()))
+
+
+def input_grad_beside(a, m, x, dl, step):
+    """forward + backward with x.requires_grad beside the plain step, alternating (the two arms see the same clocks), and the
+    stem's input-gradient launch alone by an event pair around it in one more step"""
+    from ustrun import _lib as L
+    from ustrun import resnet_engine as E
+    xg = x.clone().requires_grad_()
+
+    def step_dx():
+        for p in m.parameters():
+            p.grad = None
+        xg.grad = None
+        m(xg).backward(dl)
+
+    step_dx()
+    res = {"plain": [], "x.requires_grad": []}
+    for _ in range(3):
+        for name, fn in (("plain", step), ("x.requires_grad", step_dx)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.reps):
+                fn()
+            torch.cuda.synchronize()
+            res[name].append((time.perf_counter() - t0) / a.reps * 1e3)
+    ev = []
+    lib, orig = L.lib(), L.lib().ustrun_conv_stem_dgrad
+
+    class Timed:                                   # (the engine calls lib.ustrun_conv_stem_dgrad: an event pair around that one launch)
+        def __getattr__(self, k):
+            if k != "ustrun_conv_stem_dgrad":
+                return getattr(lib, k)
+
+            def f(*args):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                rc = orig(*args)
+                e1.record()
+                ev.append((e0, e1))
+                return rc
+            return f
+
+    real = E.L.lib
+    E.L.lib = lambda: Timed()
+    try:
+        step_dx()
+        torch.cuda.synchronize()
+    finally:
+        E.L.lib = real
+    op = sum(e0.elapsed_time(e1) for e0, e1 in ev)
+    fmt = lambda v: ", ".join(f"{t:.2f}" for t in v)
+    print(f"   forward + backward, three alternating rounds of {a.reps} steps (ms): plain {fmt(res['plain'])}; with x.requires_grad "
+          f"{fmt(res['x.requires_grad'])}; difference of the medians {sorted(res['x.requires_grad'])[1] - sorted(res['plain'])[1]:+.2f} ms; "
+          f"ustrun_conv_stem_dgrad inside the step (event pair, {len(ev)} launch): {op:.3f} ms")
 
 
 if __name__ == "__main__":

@@ -4,7 +4,8 @@ Same constructor surface (`DeepLabV2(backbone, nclass)`), the same `backbone` / 
 `base_forward` = dilated ResNet features -> four dilated 3x3 classifier convolutions (rates 6, 12, 18, 24, with bias) summed
 -> bilinear resize (align_corners=True) to the input extent, all in libustrun.so.  `pretrained=False` and `dtype` are
 additive keywords (the reference always loads ../../checkpoints/pretrained/<arch>.pth, base.py:12).  Under autograd (train mode)
-the call is differentiable with respect to the parameters: ustrun.resnet_engine.DeepLabFn runs the backward in libustrun.so.
+the call is differentiable with respect to the parameters and, when `x.requires_grad`, to the input image (also with every
+parameter frozen): ustrun.resnet_engine.DeepLabFn runs the backward in libustrun.so.
 `dtype` is "f32", "f32x3" (f32 tensors, the convolutions' products as three-term bf16 splits: f32-level results at a multiple of the
 f32 matrix rate), "bf16" or "f16".
 """

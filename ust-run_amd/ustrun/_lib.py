@@ -145,6 +145,7 @@ SIGNATURES = {
     "ustrun_unet_backward_part": (i32, [PDesc, fp, fp, vp, vp, C.POINTER(vp), i32, i32, vp]),
     "ustrun_unet_backward_io": (i32, [PDesc, fp, fp, fp, vp, vp, C.POINTER(vp), i32, i32, fp, vp]),
     "ustrun_conv_first_dgrad": (i32, [vp, fp, i32, i32, i32, i32, i32, fp, i32, vp]),
+    "ustrun_conv_stem_dgrad": (i32, [vp, fp, i32, i32, i32, i32, i32, fp, i32, vp]),
     "ustrun_aug_gather": (i32, [vp, vp, vp, i64, i32, i64, i64, vp, vp, vp]),
     "ustrun_aug_scale_crop": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "ustrun_aug_rotate": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),

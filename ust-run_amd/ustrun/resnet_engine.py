@@ -11,8 +11,11 @@ Backward (train mode): `deeplabv2_forward(..., tape=[])` records what each opera
 in reverse -- BatchNorm backward as reduce + apply (ustrun_bn_bwd_*), weight gradients on the TN GEMMs (ustrun_conv2d_wgrad),
 input gradients as convolutions of dy with the flipped / transposed weights through ustrun_conv2d_fwd (the two stride-2
 convolutions through a zero-inserted dy), the join / max-pool / resize / shifted-add adjoints of resnet_ops.hip.  `DeepLabFn`
-is the torch.autograd.Function through which `DeepLabV2.forward` is differentiable with respect to its parameters (the input
-image receives no gradient, as in the reference's training loops).
+is the torch.autograd.Function through which `DeepLabV2.forward` is differentiable with respect to its parameters and to the
+input image: with `x.requires_grad` the backward ends in ustrun_conv_stem_dgrad, the input gradient of the 7x7 / stride-2 stem
+(csrc/conv_stem_dgrad.hip), and `x.grad` is what the reference's nn.Module gives; without it the backward launches what it always
+did.  A network whose parameters are all frozen is differentiable in `x` alone (saliency maps, adversarial / VAT perturbations):
+the weight-gradient GEMMs of frozen convolutions are skipped.
 """
 from __future__ import annotations
 
@@ -338,7 +341,9 @@ def _conv_wgrad(x, dy, y, conv, grads, dt):
     nothing waits for dW before the backward returns -- the main chain's HBM-bound passes (BatchNorm apply, the join's GEMM) and small
     launches (finalizes, reduces) leave matrix pipes idle that the weight-gradient kernels use: 38.9-39.3 -> 35.9-36.0 ms per forward +
     backward at n = 16, same box (profiles/r06_ab_deeplab_wgrad_stream.log).  The side stream waits for dy's producer;
-    deeplabv2_backward joins it before it returns."""
+    deeplabv2_backward joins it before it returns.  A frozen weight gets no launch."""
+    if not conv.weight.requires_grad:
+        return
     if not _WGRAD_SIDE_STREAM:
         return _conv_wgrad_here(x, dy, y, conv, grads, dt)
     dev = dy.device
@@ -582,8 +587,9 @@ def _head_backward(rec, dlogits, dt, grads):
     return dc4
 
 
-def _stem_backward(rec, dpool, dt, grads):
-    """resnet.py:160-163 backward: gradient of the max-pool output -> stem BatchNorm and 7x7 weight gradients"""
+def _stem_backward(rec, dpool, dt, grads, dx_hw=None):
+    """resnet.py:160-163 backward: gradient of the max-pool output -> stem BatchNorm and 7x7 weight gradients; with dx_hw = the input
+    image's (H, W) also its gradient [N,3,H,W] f32 (ustrun_conv_stem_dgrad on dy0 and the f32 parameter), which is returned"""
     lib = L.lib()
     _, net, y0, p = rec
     dev = dpool.device
@@ -593,17 +599,28 @@ def _stem_backward(rec, dpool, dt, grads):
     dy0 = _bn_backward(y0, da0, True, net.bn1, grads, dt)
     pa, win, k, Cin = y0.keep
     co, Kp = y0.C, pa.C
-    pb = lib.ustrun_wgrad_partials_bytes(1, Kp, co, y0.N * y0.H * y0.W)
-    part = _scratch.get("wgrad", pb, dev)
-    dwp = torch.empty(co, Kp, device=dev)                                        # [co][ky*win + kx*Cin + ci]
-    src = pa.src()
-    L.check(lib.ustrun_conv2d_wgrad(C.byref(src), 1, dy0.data_ptr(), y0.N, y0.H, y0.W, co, 1, 1, 1, dwp.data_ptr(), 0, part.data_ptr(), pb, dt,
-                                    stream_ptr()), "ustrun_conv2d_wgrad")
-    grads[net.conv1.weight] = dwp[:, :k * win].reshape(co, k, win)[:, :, :k * Cin].reshape(co, k, k, Cin).permute(0, 3, 1, 2).contiguous()
+    if net.conv1.weight.requires_grad:
+        pb = lib.ustrun_wgrad_partials_bytes(1, Kp, co, y0.N * y0.H * y0.W)
+        part = _scratch.get("wgrad", pb, dev)
+        dwp = torch.empty(co, Kp, device=dev)                                        # [co][ky*win + kx*Cin + ci]
+        src = pa.src()
+        L.check(lib.ustrun_conv2d_wgrad(C.byref(src), 1, dy0.data_ptr(), y0.N, y0.H, y0.W, co, 1, 1, 1, dwp.data_ptr(), 0, part.data_ptr(), pb, dt,
+                                        stream_ptr()), "ustrun_conv2d_wgrad")
+        grads[net.conv1.weight] = dwp[:, :k * win].reshape(co, k, win)[:, :, :k * Cin].reshape(co, k, k, Cin).permute(0, 3, 1, 2).contiguous()
+    if dx_hw is None:
+        return None
+    H, W = dx_hw
+    assert (y0.H, y0.W) == ((H - 1) // 2 + 1, (W - 1) // 2 + 1)
+    w = net.conv1.weight.detach().contiguous()
+    dx = torch.empty(y0.N, Cin, H, W, device=dev)
+    L.check(lib.ustrun_conv_stem_dgrad(dy0.data_ptr(), w.data_ptr(), y0.N, H, W, co, Cin, dx.data_ptr(), dt, stream_ptr()),
+            "ustrun_conv_stem_dgrad")
+    return dx
 
 
-def deeplabv2_backward(net, tape, dlogits):
-    """Walk the tape of one train-mode deeplabv2_forward in reverse: {parameter: gradient (f32, the parameter's shape)}."""
+def deeplabv2_backward(net, tape, dlogits, want_dx=False):
+    """Walk the tape of one train-mode deeplabv2_forward in reverse: {parameter: gradient (f32, the parameter's shape)}; a frozen
+    convolution weight has no entry.  want_dx: returns (that dict, the input image's gradient [N,3,H,W] f32) instead."""
     dt = _DT[net.backbone.compute_dtype]
     grads = {}
     dlogits = dlogits.contiguous().float()
@@ -614,20 +631,20 @@ def deeplabv2_backward(net, tape, dlogits):
     coef3 = None
     for i in range(len(tape) - 2, 0, -1):
         G, coef3 = _block_backward(tape[i], G, dt, grads, prev=tape[i - 1] if i > 1 else None, coef3=coef3, first=(i == 1))
-    _stem_backward(tape[0], G, dt, grads)
+    dx = _stem_backward(tape[0], G, dt, grads, dx_hw=tuple(rec[3][2:]) if want_dx else None)
     _join_side_stream(dlogits.device)
-    return grads
+    return (grads, dx) if want_dx else grads
 
 
 class DeepLabFn(torch.autograd.Function):
-    """logits = DeepLabV2(x) with parameter gradients from deeplabv2_backward.  The parameters enter as inputs only so that autograd
-    routes their gradients; the engine reads them from the module."""
+    """logits = DeepLabV2(x) with parameter gradients -- and, when x requires it, the input image's -- from deeplabv2_backward.  The
+    parameters enter as inputs only so that autograd routes their gradients; the engine reads them from the module."""
 
     @staticmethod
     def forward(ctx, net, x, *params):
         tape = []
         out = deeplabv2_forward(net, x, tape)
-        ctx.net, ctx.tape, ctx.params = net, tape, params
+        ctx.net, ctx.tape, ctx.params, ctx.x_shape = net, tape, params, tuple(x.shape)
         lib = L.lib()
         ctx.debug_flags = lib.ustrun_debug_flags(0)      # (per calling thread; autograd runs backward() on its own thread)
         lib.ustrun_debug_flags(ctx.debug_flags)
@@ -638,8 +655,13 @@ class DeepLabFn(torch.autograd.Function):
         if ctx.tape is None:
             raise RuntimeError("DeepLabFn: the forward's activations were released by an earlier backward")
         restore = L.lib().ustrun_debug_flags(ctx.debug_flags)
+        dx = None
         try:
-            grads = deeplabv2_backward(ctx.net, ctx.tape, dlogits)
+            if ctx.needs_input_grad[1]:
+                grads, dx = deeplabv2_backward(ctx.net, ctx.tape, dlogits, want_dx=True)
+                assert tuple(dx.shape) == ctx.x_shape
+            else:
+                grads = deeplabv2_backward(ctx.net, ctx.tape, dlogits)
         finally:
             L.lib().ustrun_debug_flags(restore)
         ctx.tape = None
@@ -655,16 +677,18 @@ class DeepLabFn(torch.autograd.Function):
             else:
                 torch._foreach_add_(list(sink), gl)
             ctx.net._ustrun_sink_fresh = False
-            return (None, None) + (None,) * len(named)
-        return (None, None) + tuple(byid.get(id(p)) if p.requires_grad else None for p in named)
+            return (None, dx) + (None,) * len(named)
+        return (None, dx) + tuple(byid.get(id(p)) if p.requires_grad else None for p in named)
 
 
 def deeplabv2_apply(net, x):
-    """DeepLabV2.base_forward: differentiable when autograd is recording and the module trains, plain forward otherwise."""
+    """DeepLabV2.base_forward: differentiable -- in the parameters that require it and in x when x does -- when autograd is recording
+    and the module trains, plain forward otherwise."""
     if x.dim() == 4 and x.shape[1] == 1:
         x = x.expand(-1, 3, -1, -1)              # a grey image (BUSI, prostate) as three equal channels: the backbone's stem is 3-channel
     params = list(net.parameters())
-    wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+    # (the node is recorded for the input alone too: every parameter frozen, x.requires_grad -- adversarial perturbation, saliency)
+    wants_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
     if wants_grad and net.training:
         _check_input(net.backbone, x, differentiable=True)
         return DeepLabFn.apply(net, x, *params)
