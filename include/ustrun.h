@@ -323,6 +323,28 @@ int64_t ustrun_surface_metrics_work_bytes(int N, int K, int H, int W);
 int ustrun_surface_metrics(const void* pred, const void* gt, int pred_is_i64, int gt_is_i64, int N, int K, int by_class,
                            int H, int W, void* work, int64_t work_bytes, void* out, ustrun_stream_t s);
 
+/* ---- post-processing of a binary prediction, per (sample, part) plane: the reference's dataloaders/utils.py:193-204
+ * (post_processing), which fills the holes of the plane and deletes every connected component smaller than a fifth of the
+ * foreground.  pred as ustrun_surface_metrics reads it: f32 planes [N,K,H,W] binarised as (x != 0) (by_class = 0), or a class
+ * map [N,H,W], int64 or f32, whose part c is (x == c + 1) (by_class = 1); out: f32 {0,1} planes [N,K,H,W] (after filling,
+ * parts may overlap, so the result is never a class map).  For ONE plane P, background outside the image:
+ *   1 fill_holes != 0: a background pixel is a hole when no 4-connected (cross) path through background leads from it to the
+ *     image border (scipy.ndimage.binary_fill_holes, default structure); F = P | holes.  Otherwise F = P.
+ *   2 the components of F with 8-connectivity (skimage.measure.label's default for a plane); total = |F|, counted after filling.
+ *   3 component c is removed when share_den * |c| < share_num * total, in 64-bit integers.  The reference's rule
+ *     |c| / total < 0.2 in f64 is share 1 / 5 exactly for planes of at most 2^20 pixels: five equal components all stay, five
+ *     equal ones plus one pixel more all go (the empty plane, as the reference returns it); total = 0 gives the empty plane.
+ *     share_num = 0 removes nothing.
+ * fill_holes = 0 with share_num = 0 only decodes pred to planes (the ground truth's way into the same form).
+ * H, W in 1..1024 and N * K <= 65535, share_num >= 0, share_den > 0, else an error before any launch
+ * (ustrun_post_process_work_bytes: -1 + error).  work: 16-byte aligned, owned by the caller; everything is asynchronous on s,
+ * nothing is allocated, nothing waits for the device or reads from it; the components are a unique partition found with
+ * integer atomics only: equal bits on every run.                                                                          */
+int64_t ustrun_post_process_work_bytes(int N, int K, int H, int W);
+int ustrun_post_process(const void* pred, int pred_is_i64, int N, int K, int by_class, int H, int W,
+                        int fill_holes, int share_num, int share_den,
+                        void* work, int64_t work_bytes, float* out, ustrun_stream_t s);
+
 /* ---- SGD(momentum, weight decay) + EMA teacher over flat buffers: train.py:512,848,87-93 ------
  * g += wd*p; v = first ? g : mu*v + g; p -= lr*v; t = alpha*t + (1-alpha)*p                    */
 /* ---- dynamic loss scale of the IEEE-half path: torch.cuda.amp.GradScaler as train.py:552,842-845 uses it, on the device.

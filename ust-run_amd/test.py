@@ -3,13 +3,14 @@
 
 Same command line (flag names and defaults of test.py:19-32; `--dataset` also accepts BUSI, which the reference
 trains but does not list here); additive flags: --synthetic, --data_root, --test_batches, --backend_dtype, --seed, --surface_metrics,
---save_dir, --save_img_mode.  Loads
+--save_dir, --save_img_mode, --post_process.  Loads
 `../model/<dataset>/<save_name>/unet_avg_dice_best_model.pth` (a plain state_dict with the reference's keys, test.py:241)
 and prints the per-domain and mean Dice of ustrun.evaluate.validate; `--surface_metrics 1` adds the reference's
 dc / jc / hd / asd lines (test.py:117-136,160-176), computed on the device instead of with medpy.  `--save_img` writes the
 reference's one picture per test image (test.py:110-113) under ./img/save (or --save_dir), rendered on the device
-(ustrun/render.py); `--save_img_mode contour` draws the library's other view, prediction against ground truth.  Batches come from the
-seeded synthetic generator, or with --synthetic 0 from the test splits under --data_root (ustrun/datasets.py).
+(ustrun/render.py); `--save_img_mode contour` draws the library's other view, prediction against ground truth.
+`--post_process 1` runs every part of the prediction through the reference's post_processing (dataloaders/utils.py:193-204) on the
+device before it is measured or drawn.  Batches come from the seeded synthetic generator, or with --synthetic 0 from the test splits under --data_root (ustrun/datasets.py).
 """
 import argparse
 import logging
@@ -44,6 +45,8 @@ parser.add_argument('--image_size', type=int, default=0, help='patch extent over
 parser.add_argument('--save_dir', type=str, default='./img/save', help='--save_img: where the pictures go (test.py:113)')
 parser.add_argument('--save_img_mode', default='mask', choices=['mask', 'contour'],
                     help='--save_img: draw_mask_and_save (the reference\'s) or draw_contour_and_save')
+parser.add_argument('--post_process', type=int, default=0, choices=[0, 1],
+                    help='1: fill holes and drop components below a fifth of the foreground before measuring')
 
 DOMAINS = {"fundus": 4, "prostate": 6, "MNMS": 4, "BUSI": 1}     # test.py:209-223
 
@@ -73,7 +76,8 @@ def main(args):
     path = args.load_path or '../model/{}/{}/{}_avg_dice_best_model.pth'.format(args.dataset, args.save_name, args.model)
     model.load_state_dict(torch.load(path, map_location="cuda"))
     return validate(args.dataset, model, make_loaders(args, C, H), epoch=args.lb_domain, surface_metrics=bool(args.surface_metrics),
-                    save_dir=args.save_dir if args.save_img else None, save_mode=args.save_img_mode)
+                    save_dir=args.save_dir if args.save_img else None, save_mode=args.save_img_mode,
+                    post_process=bool(args.post_process))
 
 
 if __name__ == "__main__":

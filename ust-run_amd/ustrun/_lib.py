@@ -95,6 +95,8 @@ SIGNATURES = {
     "ustrun_dice_counts": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "ustrun_surface_metrics_work_bytes": (i64, [i32, i32, i32, i32]),
     "ustrun_surface_metrics": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp]),
+    "ustrun_post_process_work_bytes": (i64, [i32, i32, i32, i32]),
+    "ustrun_post_process": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, fp, vp]),
     "ustrun_sgd_ema": (i32, [fp, fp, fp, fp, i64, f32, f32, f32, i32, f32, f32, vp]),
     "ustrun_amp_check": (i32, [fp, i64, fp, vp]),
     "ustrun_sgd_ema_scaled": (i32, [fp, fp, fp, fp, i64, f32, f32, f32, i32, f32, f32, fp, vp]),

@@ -14,6 +14,10 @@ loss the reference computes is never accumulated there and is not computed here.
 `validate(..., save_dir=...)` is the reference's `--save_img` (test.py:110-113): the coalesced batch is rendered once on the
 device (ustrun/render.py), its uint8 [N,H,W,3] block is copied to the host and written as one PNG per image under the
 reference's file names, on a few host threads beside the next batches' forwards (render.PngWriter).  Nothing else changes: the metrics and the logged lines are those of a run without it.
+
+`validate(..., post_process=True)` applies the reference's `post_processing` (dataloaders/utils.py:193-204: holes filled, components
+below a fifth of the foreground removed) to every part of the prediction before anything is measured or drawn, on the device
+(ustrun_post_process).  Filled parts may overlap, so from there on prediction and ground truth are float planes [N,parts,H,W].
 """
 import logging
 import os
@@ -37,9 +41,22 @@ def predict(dataset, logits):
     return F.pseudo_label(logits, 0.5, mode)[0]
 
 
-def sample_dice(dataset, pred, mask):
-    """Per-sample, per-part Dice [N, parts] from device overlap counts (utils/metrics.py:114-146 on every sample)."""
-    if dataset == "MNMS":
+def _part_kw(dataset):
+    """How the dataset's prediction and ground truth name their parts: MNMS class maps by value, the others as planes."""
+    return dict(by_class=True, n_classes=3) if dataset == "MNMS" else {}
+
+
+def post_processed(dataset, pred, mask):
+    """-> (prediction after the reference's post_processing, ground truth), both as float planes [N, parts, H, W]: the mask
+    goes through the same call with both steps off, which only decodes it."""
+    kw = _part_kw(dataset)
+    return F.post_process(pred, **kw), F.post_process(mask, fill_holes=False, min_share=None, **kw)
+
+
+def sample_dice(dataset, pred, mask, planes=False):
+    """Per-sample, per-part Dice [N, parts] from device overlap counts (utils/metrics.py:114-146 on every sample).
+    planes: pred and mask are float planes [N, parts, H, W] whatever the dataset (`post_processed`)."""
+    if dataset == "MNMS" and not planes:
         cnt = F.dice_counts(pred, mask, by_class=True, n_classes=3)
     else:
         cnt = F.dice_counts(pred, mask)
@@ -47,10 +64,10 @@ def sample_dice(dataset, pred, mask):
     return metrics.dice_from_counts(c[..., 0], c[..., 1], c[..., 2])
 
 
-def sample_metrics(dataset, pred, mask):
+def sample_metrics(dataset, pred, mask, planes=False):
     """Per-sample, per-part (dice, dc, jc, hd95, asd), [N, parts] each: the Dice of `sample_dice` and the four medpy metrics
     of train.py:306-320 (hd95 = asd = 100 for an empty prediction; an empty ground truth raises, as medpy does)."""
-    kw = dict(by_class=True, n_classes=3) if dataset == "MNMS" else {}
+    kw = {} if planes else _part_kw(dataset)
     cnt, rec = F.dice_counts(pred, mask, **kw), F.surface_metrics(pred, mask, **kw)
     c, r = cnt.cpu().numpy(), rec.cpu().numpy()
     cf = c.astype(np.float64)
@@ -65,7 +82,7 @@ def batch_dice(dataset, pred, mask):
 
 @torch.no_grad()
 def validate(dataset, model, loaders, epoch=0, log=logging.info, coalesce=64, surface_metrics=False, save_dir=None,
-             save_mode="mask"):
+             save_mode="mask", post_process=False):
     """loaders: one iterable of (image, raw label) batches per domain (any device; moved to the model's).
     Returns (val_dice[parts], per_domain[domain][parts]); leaves the model in train mode, as the reference does.
     surface_metrics=True: returns (val_dice, per_domain, extra) with extra[m] = {"val": [parts], "per_domain": [domain][parts]}
@@ -78,7 +95,11 @@ def validate(dataset, model, loaders, epoch=0, log=logging.info, coalesce=64, su
 
     save_dir: also write one picture per image there, `{domain}_{num}_{avg}.png` as test.py:113 names them (domain from 1, num
     the running image count from 1 over all domains, avg = round(mean over the parts of the Dice of the image's LOADER batch, 4));
-    save_mode "mask" is the reference's draw_mask_and_save, "contour" its draw_contour_and_save (prediction against ground truth)."""
+    save_mode "mask" is the reference's draw_mask_and_save, "contour" its draw_contour_and_save (prediction against ground truth).
+
+    post_process=True: every part of the prediction goes through the reference's post_processing first (`post_processed`); Dice,
+    the surface metrics and the pictures are those of the processed prediction (one emptied by it takes hd = asd = 100 like any
+    empty prediction), the logged lines, the averaging and the file names keep their form."""
     if save_mode not in ("mask", "contour"):
         raise ValueError("save_mode is 'mask' or 'contour', got %r" % (save_mode,))
     if save_dir is not None:
@@ -102,9 +123,11 @@ def validate(dataset, model, loaders, epoch=0, log=logging.info, coalesce=64, su
         image = torch.cat([b[0] for b in pending], 0) if len(pending) > 1 else pending[0][0]
         label = torch.cat([b[1] for b in pending], 0) if len(pending) > 1 else pending[0][1]
         pred, mask = predict(dataset, model(image)), decode_labels(dataset, label)
+        if post_process:
+            pred, mask = post_processed(dataset, pred, mask)
         if surface_metrics:
             try:
-                d, *x = sample_metrics(dataset, pred, mask)
+                d, *x = sample_metrics(dataset, pred, mask, planes=post_process)
             except metrics.EmptyGroundTruth as e:           # e.sample counts over the coalesced loader batches
                 b, n = 0, e.sample
                 while n >= len(pending[b][0]):
@@ -112,7 +135,7 @@ def validate(dataset, model, loaders, epoch=0, log=logging.info, coalesce=64, su
                     b += 1
                 raise metrics.EmptyGroundTruth(n, e.part, "domain %d, loader batch %d, " % (seen[0] + 1, seen[1] + b)) from None
         else:
-            d = sample_dice(dataset, pred, mask)
+            d = sample_dice(dataset, pred, mask, planes=post_process)
         if save_dir is not None:                            # one render and one uint8 [N,H,W,3] copy per coalesced batch
             if save_mode == "mask":
                 rgb = render.render_mask(image, pred, parts=len(part))

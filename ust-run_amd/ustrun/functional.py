@@ -366,6 +366,31 @@ def surface_metrics(pred, gt, by_class=False, n_classes=1):
     return out
 
 
+def post_process(pred, by_class=False, n_classes=1, fill_holes=True, min_share=(1, 5)):
+    """The reference's dataloaders/utils.py:193-204 `post_processing` on every (sample, part) plane of `pred` (taken as
+    `surface_metrics` takes it) -> float32 {0,1} planes [N,K,H,W] on the device (ustrun_post_process): holes filled (4-connected
+    background that does not reach the image border), then every 8-connected component c with den * |c| < num * |filled plane|
+    removed, min_share = (num, den); None switches the removal off.  With fill_holes=False and min_share=None the call only
+    decodes `pred` to planes.  Filled parts may overlap, so the result is never a class map."""
+    lib = L.lib()
+    pred = pred.contiguous()
+    if pred.dim() < 3 or (by_class and pred.dim() != 3):
+        raise RuntimeError(f"post_process: pred {tuple(pred.shape)} must be [N,(K,)H,W], a class map [N,H,W] with by_class")
+    if pred.dtype not in (torch.float32, torch.int64) or not pred.is_cuda:
+        raise RuntimeError(f"post_process: pred must be a float32 or int64 HIP tensor, got {pred.dtype} on {pred.device}")
+    N, (H, W) = pred.shape[0], pred.shape[-2:]
+    K = n_classes if by_class else (pred.shape[1] if pred.dim() == 4 else 1)
+    num, den = (0, 1) if min_share is None else (int(min_share[0]), int(min_share[1]))
+    nb = lib.ustrun_post_process_work_bytes(N, K, H, W)
+    if nb < 0:
+        L.check(1, "ustrun_post_process_work_bytes")
+    work = torch.empty(nb, dtype=torch.uint8, device=pred.device)
+    out = torch.empty((N, K, H, W), dtype=torch.float32, device=pred.device)
+    L.check(lib.ustrun_post_process(pred.data_ptr(), int(pred.dtype == torch.int64), N, K, int(by_class), H, W, int(bool(fill_holes)),
+                                    num, den, work.data_ptr(), nb, out.data_ptr(), stream_ptr()), "ustrun_post_process")
+    return out
+
+
 def sgd_ema(p, g, v, t, lr, momentum, weight_decay, first, alpha, grad_scale=1.0):
     """Fused SGD(momentum, wd) step on flat f32 buffers + EMA teacher update (train.py:512,848,87-93)."""
     lib = L.lib()
