@@ -160,6 +160,13 @@ int ustrun_bn_bwd_reduce(const void* da, const void* dp, const void* y, const fl
 int ustrun_bn_bwd_apply(const void* da, const void* dp, const void* y, const float* scale,
                         const float* shift, const float* coef, int N, int H, int W, int C, void* dy,
                         int dtype, ustrun_stream_t s);
+/* The same pass (plain, 16-bit storage, C / 8 a power of two <= 256) for the layer under the classification head when the head's
+ * input gradient was not stored: da[p][c] = sum_k dlogits[k][p] head_w[k][c] is formed again per pixel, rounded to the storage type as
+ * ustrun_head_bwd stores it, and applied.  dlogits [passes][N][K][H][W] f32, head_w [K][C]; y / dy hold `passes` passes of N images,
+ * scale / shift `aff_stride` floats apart per pass, coef [passes][3][C].  Bit-identical to ustrun_head_bwd + ustrun_bn_bwd_apply.    */
+int ustrun_bn_bwd_apply_head(const float* dlogits, const float* head_w, const void* y, const float* scale, const float* shift,
+                             const float* coef, int N, int H, int W, int C, int K, void* dy, int dtype, int passes,
+                             int64_t aff_stride, ustrun_stream_t s);
 
 /* ---- conv3x3 input gradient (autograd of unet_parts.py:16,19) ------------------------------
  * da = conv3x3(dy, flipped/transposed w).  Channels [0,C0) go to da0[N,H,W,C0]; channels
@@ -186,6 +193,14 @@ int ustrun_bn_bwd_finalize_stat(float* stat, int rows_per_pass, int passes, int 
                                 int accumulate, float* coef, ustrun_stream_t s);
 /* ---- conv3x3 weight gradient: dw[Cout][Cin][3][3] (torch layout, f32) ---------------------- */
 int64_t ustrun_wgrad_partials_bytes(int nseg, int Cin, int Cout, int64_t npix);
+/* The first convolution's weight gradient (NCHW f32 source of C <= 3 channels -> 64, 16-bit storage, the streaming kernel's
+ * shapes; anything else is an error) with the layer's BatchNorm-backward apply pass on load: dY = ustrun_bn_bwd_apply(da, y) is formed
+ * piece by piece in the kernel's loader and never stored.  Image n takes the constants of pass n / gN (gN = 0: one pass): scale /
+ * shift + pass * aff_stride floats, coef + pass * 3 * 64.  partials as for ustrun_conv3x3_wgrad (ustrun_wgrad_partials_bytes(9, C, 64,
+ * N H W)).  Bit-identical to ustrun_bn_bwd_apply + ustrun_conv3x3_wgrad.                                                          */
+int ustrun_conv_first_wgrad_bn(const ustrun_src_t* src, const void* da, const void* y, const float* scale, const float* shift,
+                               const float* coef, int gN, int64_t aff_stride, int N, int H, int W, int Cout, float* dw,
+                               int accumulate, float* partials, int64_t partials_bytes, int dtype, ustrun_stream_t s);
 int ustrun_conv3x3_wgrad(const ustrun_src_t* srcs, int nsrc, const void* dy, int N, int H, int W,
                          int Cout, float* dw, int accumulate, float* partials, int64_t partials_bytes,
                          int dtype, ustrun_stream_t s);
@@ -544,6 +559,11 @@ int ustrun_debug_last_wgrad_variant(void);
  * 0x424E0000 | pass << 8 (0 reduce, 1 apply) | element bytes << 4 | even-sized pooled windows << 2 | pooled << 1 |
  * eight channels (16 bytes) per lane; 0 before any                                                              */
 int ustrun_debug_last_bn_variant(void);
+/* the routes the calling thread's last ustrun_unet_backward / _part / _io call took at the two full-resolution layers:
+ * bit 0: layer 17 (under the head) -- the head stored no input gradient, the BatchNorm-backward apply pass formed it from dlogits;
+ * bit 1: layer 0 -- no apply pass, the first convolution's weight gradient formed dY from da and y on load.
+ * A call that does not cover the layer (parts) leaves its bit clear.                                                            */
+int ustrun_debug_last_backward_route(void);
 /* test aid, host only (no launch, no device access): the number of BatchNorm-statistics rows the kernel that would serve a
  * k x k convolution of a dense NHWC source [N, Cin] -> [N, Ho, Wo, Cout] writes.  tests/test_host_logic.py sweeps shapes
  * with it: the count must never exceed ustrun_conv_mtiles(N, Ho, Wo, Cout), which is what callers allocate           */
@@ -594,7 +614,11 @@ int ustrun_debug_flags(int flags);
  *   before they took the pass's constants per image (A/B runs).
  * bit 2 (4): the 64 -> 64 streaming kernel keeps its uniform strip split (round 6: the flat plan gives every block the same number
  *   of row steps at any image count) -- A/B runs.
- * bit 3 (8): ustrun_conv1x1_dgrad_join never fuses (*fused = 0) -- A/B runs and the tests of the unfused path.                 */
+ * bit 3 (8): ustrun_conv1x1_dgrad_join never fuses (*fused = 0) -- A/B runs and the tests of the unfused path.
+ * bit 4 (16): ustrun_unet_backward stores the head's input gradient and runs layer 17's BatchNorm-backward apply pass over it, and
+ *   runs layer 0's apply pass in front of the first convolution's weight gradient, as before those two round trips were dropped
+ *   (ustrun_debug_last_backward_route reads 0) -- A/B runs and the equality tests.  The workspace is the same either way.
+ *   bit 5 (32): layer 17's round trip alone, bit 6 (64): layer 0's alone -- each half timed with the other in place.           */
 int ustrun_debug_flags2(int flags);
 /* Operator-level declaration (per calling thread; returns the previous value): while `allow` is nonzero, the convolution entry
  * points accept a batch whose LAST pass is shorter than ustrun_src_t::gN (N % gN != 0 -- the caller then owns a constants table of

@@ -721,12 +721,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* da, cons
 // their occupancy that is about half of what 8 TB/s x the memory latency asks of a CU, and the plain apply pass ran at
 // 4.8-5.1 TB/s where the pooled one (nine loads per thread) reaches 5.5.  Here a lane owns 8 channels of a pixel: thread =
 // (octet tid % G8, pixel lane tid / G8), G8 = C / 8 a power of two <= 256; the arithmetic is the same per element.
-struct F8 { f32x4 lo, hi; };
-__device__ __forceinline__ F8 up8(bf16x8 v) {
-    return F8{(f32x4){(float)v[0], (float)v[1], (float)v[2], (float)v[3]}, (f32x4){(float)v[4], (float)v[5], (float)v[6], (float)v[7]}};
-}
-__device__ __forceinline__ F8 ld8f(const float* p) { return F8{*(const f32x4*)p, *(const f32x4*)(p + 4)}; }
-
+// (F8, up8, ld8f and the apply statement bn_bwd_apply8 live in common.h: the first convolution's weight gradient uses them too)
 __global__ __launch_bounds__(256) void bn_bwd_apply_x8_kernel(const elt_t* __restrict__ da, const elt_t* __restrict__ y,
                                                              const float* __restrict__ scale, const float* __restrict__ shift,
                                                              const float* __restrict__ coef, long npix, int C, int G8,
@@ -742,18 +737,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_x8_kernel(const elt_t* __res
     const long stride = (long)gridDim.x * PL;
     constexpr int U = 2;
     long w = (long)blockIdx.x * PL + pl;
-    auto one = [&](bf16x8 yb, bf16x8 db) {
-        const F8 yv = up8(yb), dv = up8(db);
-        bf16x8 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float al = yv.lo[j] * sc.lo[j] + sh.lo[j], ah = yv.hi[j] * sc.hi[j] + sh.hi[j];
-            const float zl = al > 0.f ? dv.lo[j] : 0.f, zh = ah > 0.f ? dv.hi[j] : 0.f;
-            o[j] = (elt_t)(k0.lo[j] * zl + k1.lo[j] * yv.lo[j] + k2.lo[j]);
-            o[4 + j] = (elt_t)(k0.hi[j] * zh + k1.hi[j] * yv.hi[j] + k2.hi[j]);
-        }
-        return o;
-    };
+    auto one = [&](bf16x8 yb, bf16x8 db) { return bn_bwd_apply8(yb, db, sc, sh, k0, k1, k2); };
     for (; w + (U - 1) * stride < npix; w += U * stride) {
         bf16x8 yb[U], db[U];
 #pragma unroll
@@ -763,6 +747,69 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_x8_kernel(const elt_t* __res
     }
     for (; w < npix; w += stride)
         *(bf16x8*)(dy + w * C + c) = one(*(const bf16x8*)(y + w * C + c), *(const bf16x8*)(da + w * C + c));
+}
+
+// The same pass for the layer under the head, whose da nobody stored: da[p][c] = sum_k dl[k][p] w[k][c] is formed again from the K
+// f32 values of dl per pixel (8 B at K = 2, against 128 B of stored gradient) exactly as head_bwd_kernel forms it -- head_grad4,
+// rounded to the storage type as its store rounds it -- and goes through bn_bwd_apply8 like a loaded one.  dl is NCHW: dl[(n K + k) HW
+// + hw]; a trip's first pixel is block-uniform, so the division by HW runs once per trip on the scalar unit and a lane only steps
+// over image ends.  KT > 0: the class count at compile time; KT == 0: any K <= HEAD_KMAX.
+constexpr int HEAD_KMAX = 8;
+template <int KT>
+__global__ __launch_bounds__(256) void bn_bwd_apply_head_x8_kernel(const float* __restrict__ dl, const float* __restrict__ w_head,
+                                                                  const elt_t* __restrict__ y, const float* __restrict__ scale,
+                                                                  const float* __restrict__ shift, const float* __restrict__ coef,
+                                                                  long npix, int HW, int C, int G8, int Krt, elt_t* __restrict__ dy,
+                                                                  const PassOff po) {
+    constexpr int KN = KT > 0 ? KT : HEAD_KMAX;
+    const int K = KT > 0 ? KT : Krt;
+    {
+        const long g = blockIdx.y;
+        dl += g * npix * K; y += g * po.act; dy += g * po.act;
+        scale += g * po.aff; shift += g * po.aff; coef += g * po.coef;
+    }
+    const int PL = 256 / G8;
+    const int c = 8 * (threadIdx.x % G8), pl = threadIdx.x / G8;
+    const F8 sc = ld8f(scale + c), sh = ld8f(shift + c), k0 = ld8f(coef + c), k1 = ld8f(coef + C + c), k2 = ld8f(coef + 2 * C + c);
+    f32x4 wlo[KN], whi[KN];
+#pragma unroll
+    for (int k = 0; k < KN; ++k) {
+        const bool on = KT > 0 || k < K;
+        wlo[k] = on ? *(const f32x4*)(w_head + k * C + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        whi[k] = on ? *(const f32x4*)(w_head + k * C + c + 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    const long stride = (long)gridDim.x * PL;
+    constexpr int U = 2;
+    // the K values of dl at pixel wb + pl (wb: the trip's first pixel, block-uniform)
+    auto load_d = [&](long wb, float (&d)[KN]) {
+        const unsigned n0 = (unsigned)wb / (unsigned)HW;              // npix < 2^31 (checked on the host)
+        long n = n0;
+        int hw = (int)(wb - (long)n0 * HW) + pl;
+        while (hw >= HW) { hw -= HW; ++n; }
+        const float* p = dl + n * K * HW + hw;
+#pragma unroll
+        for (int k = 0; k < KN; ++k) d[k] = (KT > 0 || k < K) ? p[(long)k * HW] : 0.f;
+    };
+    auto grad = [&](const float (&d)[KN]) {
+        const f32x4 lo = head_grad4<KN, KT == 0>(d, wlo, K), hi = head_grad4<KN, KT == 0>(d, whi, K);
+        bf16x8 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { o[j] = (elt_t)lo[j]; o[4 + j] = (elt_t)hi[j]; }
+        return o;
+    };
+    long wb = (long)blockIdx.x * PL;
+    for (; wb + pl + (U - 1) * stride < npix; wb += U * stride) {
+        bf16x8 yb[U]; float d[U][KN];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { yb[u] = *(const bf16x8*)(y + (wb + pl + u * stride) * C + c); load_d(wb + u * stride, d[u]); }
+#pragma unroll
+        for (int u = 0; u < U; ++u) *(bf16x8*)(dy + (wb + pl + u * stride) * C + c) = bn_bwd_apply8(yb[u], grad(d[u]), sc, sh, k0, k1, k2);
+    }
+    for (; wb + pl < npix; wb += stride) {
+        float d[KN];
+        load_d(wb, d);
+        *(bf16x8*)(dy + (wb + pl) * C + c) = bn_bwd_apply8(*(const bf16x8*)(y + (wb + pl) * C + c), grad(d), sc, sh, k0, k1, k2);
+    }
 }
 
 __global__ __launch_bounds__(256) void bn_bwd_reduce_x8_kernel(const elt_t* __restrict__ da, const elt_t* __restrict__ y,
@@ -1123,7 +1170,39 @@ int bn_bwd_apply_passes(const void* da, const void* dp, const void* y, const flo
     USTRUN_LAUNCH_CHECK("bn_bwd_apply");
     return 0;
 }
+
+// layer 17's apply pass without a stored da: see bn_bwd_apply_head_x8_kernel.  dlogits [passes][N][K][H][W] f32, head_w [K][C]
+bool bn_bwd_apply_head_ok(int C, int K, int dtype) { return x8_ok(C, false, dtype) && K >= 1 && K <= HEAD_KMAX; }
+int bn_bwd_apply_head_passes(const float* dlogits, const float* head_w, const void* y, const float* scale, const float* shift,
+                             const float* coef, int N, int H, int W, int C, int K, void* dy, int dtype, int passes,
+                             long act_elems, long aff_stride, hipStream_t s) {
+    USTRUN_CHECK(dlogits && head_w && y && scale && shift && coef && dy, "bn_bwd_apply_head: null pointer");
+    USTRUN_CHECK(bn_bwd_apply_head_ok(C, K, dtype), "bn_bwd_apply_head: C=%d K=%d dtype %d not served", C, K, dtype);
+    USTRUN_CHECK(N > 0 && H > 0 && W > 0 && passes >= 1, "bn_bwd_apply_head: bad extent");
+    USTRUN_CHECK(!(((uintptr_t)head_w | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)coef) & 15) && aff_stride % 4 == 0,
+                 "bn_bwd_apply_head: constants must be 16-byte aligned");
+    const long npix = (long)N * H * W;
+    USTRUN_CHECK(npix < (1L << 31), "bn_bwd_apply_head: %ld pixels per pass", npix);
+    const int G = C / 8, PL = 256 / G;
+    long blocks = (npix + (long)PL * 4 - 1) / ((long)PL * 4);
+    if (blocks > 4096) blocks = 4096;
+    const PassOff po = {act_elems, 0, aff_stride, 0, 3L * C};
+#define USTRUN_BN_AH(KT)                                                                                                           \
+    hipLaunchKernelGGL(bn_bwd_apply_head_x8_kernel<KT>, dim3((int)blocks, passes), dim3(256), 0, s, dlogits, head_w, (const elt_t*)y, \
+                       scale, shift, coef, npix, H * W, C, G, K, (elt_t*)dy, po)
+    if (K == 2) USTRUN_BN_AH(2); else if (K == 4) USTRUN_BN_AH(4); else USTRUN_BN_AH(0);
+#undef USTRUN_BN_AH
+    USTRUN_LAUNCH_CHECK("bn_bwd_apply_head");
+    return 0;
+}
 }  // namespace ustrun
+
+extern "C" int ustrun_bn_bwd_apply_head(const float* dlogits, const float* head_w, const void* y, const float* scale,
+                                        const float* shift, const float* coef, int N, int H, int W, int C, int K, void* dy,
+                                        int dtype, int passes, int64_t aff_stride, ustrun_stream_t s) {
+    return bn_bwd_apply_head_passes(dlogits, head_w, y, scale, shift, coef, N, H, W, C, K, dy, dtype, passes, (long)N * H * W * C,
+                                    (long)aff_stride, (hipStream_t)s);
+}
 
 extern "C" int ustrun_bn_bwd_finalize_stat(float* stat, int rows_per_pass, int passes, int C, int64_t count, const float* gamma,
                                            const float* mean, const float* rstd, int64_t aff_stride, float* dgamma, float* dbeta,

@@ -377,6 +377,7 @@ __device__ __forceinline__ u32x4 and4(u32x4 d, unsigned m) {
 struct WgOp16 : WgPieces<128, 1> {                       // 16-bit dY (2 KB per step), used as stored: one MFMA per column half
     typedef elt_t dy_t;
     typedef bf16x8 afrag;
+    static constexpr bool BN = false;
     static constexpr const char* NAME = "conv_first_wgrad_stream";
     static __device__ __forceinline__ void stage(char* sl, int lane, const u32x4 (&d)[NP], const unsigned (&m)[NP]) {
 #pragma unroll
@@ -394,9 +395,20 @@ struct WgOp16 : WgPieces<128, 1> {                       // 16-bit dY (2 KB per 
     }
 };
 
+// The same with dY formed on load: the layer's BatchNorm-backward apply pass, dy = k0 (a > 0 ? da : 0) + k1 y + k2, runs on each
+// 16-byte piece (8 channels of a pixel: the lane's channel group lane % 8 is the same for all its pieces, its 40 constants live in
+// registers) of da and y as they come out of the prefetch registers -- bn_bwd_apply8, the statement of the apply kernel, rounded to
+// the storage type like its store -- and the MFMA gets the registers the stored dy would have filled.  4 KB per step instead of 2,
+// no apply pass (read da, y; write dy) in front and no dy to read back.
+struct WgOp16Bn : WgOp16 {
+    static constexpr bool BN = true;
+    static constexpr const char* NAME = "conv_first_wgrad_stream_bn";
+};
+
 struct WgOpX3 : WgPieces<256, 3> {                       // dtype USTRUN_F32X3: f32 dY (4 KB per step), both operands split into three
     typedef float dy_t;                                  // bf16 terms at use (x3.hip's arithmetic: six MFMAs per product, f32-level
     struct afrag { b16x8 p[3]; };                        // result), three LDS planes per slot
+    static constexpr bool BN = false;
     static constexpr const char* NAME = "conv_first_wgrad_x3";
     static __device__ __forceinline__ void stage(char* sl, int lane, const u32x4 (&d)[NP], const unsigned (&m)[NP]) {
 #pragma unroll
@@ -425,11 +437,14 @@ struct WgOpX3 : WgPieces<256, 3> {                       // dtype USTRUN_F32X3: 
     }
 };
 
+// Op::BN: dy holds da; y and the BatchNorm-backward constants of the pass an image belongs to (image / gN) come with it
+struct CfWgradBn { const void* y; const float* scale; const float* shift; const float* coef; int gN; int aff_stride; int coef_stride; };
+
 template <typename Op, int D>
 __global__ __launch_bounds__(256) void conv_first_wgrad_stream_kernel(const float* __restrict__ x, int sN, int sC, int sH, int C,
                                                                       int H, int W, int xbytes, const typename Op::dy_t* __restrict__ dy,
                                                                       int dybytes, float* __restrict__ partials, int strips, int segs,
-                                                                      int seg_rows, int items) {
+                                                                      int seg_rows, int items, const CfWgradBn bn) {
     constexpr int NP = Op::NP;
     extern __shared__ __attribute__((aligned(16))) char dys[];        // Op::LDS bytes: 4 waves x 2 slots, then the final sum
     const int tid = threadIdx.x, lane = tid & 63;
@@ -472,6 +487,18 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_stream_kernel(const floa
         const int lbase = dy_lane_base(lane);
         u32x4 xr[D][2], dr[D][NP];
         unsigned rm[D];                                               // per slot: all ones where the lane's x row lies in the image
+        // Op::BN: y's pieces ride with da's through the same offsets; the lane's channel group and the item's pass are fixed
+        constexpr int NY = Op::BN ? NP : 1;
+        u32x4 yr[D][NY];
+        __amdgpu_buffer_rsrc_t ry = rd;
+        F8 bsc = {}, bsh = {}, bk0 = {}, bk1 = {}, bk2 = {};
+        if constexpr (Op::BN) {
+            ry = __builtin_amdgcn_make_buffer_rsrc((void*)bn.y, 0, dybytes, 0x00020000);
+            const int ps = img / bn.gN, c8 = 8 * (lane % Op::PPP);
+            const float* cf = bn.coef + (long)ps * bn.coef_stride + c8;
+            bsc = ld8f(bn.scale + (long)ps * bn.aff_stride + c8); bsh = ld8f(bn.shift + (long)ps * bn.aff_stride + c8);
+            bk0 = ld8f(cf); bk1 = ld8f(cf + 64); bk2 = ld8f(cf + 128);
+        }
         auto prefetch = [&](int u, int y) {
             const int yy = y + ikh - 1;
             rm[u] = (y < r1 && (unsigned)yy < (unsigned)H) ? 0xffffffffu : 0u;
@@ -482,6 +509,11 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_stream_kernel(const floa
 #pragma unroll
             for (int i = 0; i < NP; ++i)
                 dr[u][i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rd, dofs + i * Op::PXS * Op::PXB, 0, 0));
+            if constexpr (Op::BN) {
+#pragma unroll
+                for (int i = 0; i < NP; ++i)
+                    yr[u][i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ry, dofs + i * Op::PXS * Op::PXB, 0, 0));
+            }
         };
         auto consume = [&](int u, int par, bool live) {
             char* sl = slot + par * Op::SLOT;
@@ -489,6 +521,12 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_stream_kernel(const floa
             unsigned m[NP];
 #pragma unroll
             for (int i = 0; i < NP; ++i) m[i] = dm[i] & lm;
+            if constexpr (Op::BN) {     // (pieces outside the image or the segment become some k2 here and zero under the mask in stage)
+#pragma unroll
+                for (int i = 0; i < NP; ++i)
+                    dr[u][i] = __builtin_bit_cast(u32x4, bn_bwd_apply8(__builtin_bit_cast(bf16x8, yr[u][i]), __builtin_bit_cast(bf16x8, dr[u][i]),
+                                                                       bsc, bsh, bk0, bk1, bk2));
+            }
             Op::stage(sl, lane, dr[u], m);
             unsigned v[8];
 #pragma unroll
@@ -760,13 +798,14 @@ int launch_reduce(const float* partials, int slabs, int C, float* dw, int accumu
 
 // plan and launch the streaming kernel (the caller has asked conv_first_wgrad_stream_ok), then the slab reduce
 template <typename Op>
-int launch_wgrad_stream(const ustrun_src_t& s, const void* dy, int N, float* dw, int accumulate, float* partials, hipStream_t st) {
+int launch_wgrad_stream(const ustrun_src_t& s, const void* dy, int N, float* dw, int accumulate, float* partials, hipStream_t st,
+                        const CfWgradBn bn = {}) {
     const CfWgradPlan p = conv_first_wgrad_plan(N, s.H, s.W);
     const auto kernel = conv_first_wgrad_stream_kernel<Op, 4>;
     if (Op::LDS > 65536) USTRUN_TRY(ensure_dynamic_lds((const void*)kernel, Op::LDS, Op::NAME));
     hipLaunchKernelGGL(kernel, dim3(p.blocks), dim3(256), Op::LDS, st, (const float*)s.ptr, (int)s.sN, (int)s.sC, (int)s.sH, s.C, s.H, s.W,
                        (int)((long)N * s.sN * 4), (const typename Op::dy_t*)dy, (int)((long)N * s.H * s.W * Op::PXB), partials, p.strips,
-                       p.nseg, p.seg_rows, (int)p.items);
+                       p.nseg, p.seg_rows, (int)p.items, bn);
     USTRUN_LAUNCH_CHECK(Op::NAME);
     return launch_reduce(partials, p.blocks, s.C, dw, accumulate, st);
 }
@@ -792,6 +831,24 @@ int conv_first_wgrad(const ustrun_src_t& s, const void* dy, int dy_esz, int N, f
                        (long)s.sW, s.C, s.H, s.W, (const elt_t*)dy, partials, tx, ty, ttotal, per);
     USTRUN_LAUNCH_CHECK("conv_first_wgrad");
     return launch_reduce(partials, blocks, s.C, dw, accumulate, st);
+}
+
+
+// the 16-bit streaming weight gradient with layer 0's BatchNorm-backward apply pass on load (WgOp16Bn): dy = apply(da, y) is never stored
+bool conv_first_wgrad_bn_ok(const ustrun_src_t& s, int N, int H, int W, int Cout, int dtype) {
+    return dtype == USTRUN_D16 && conv_first_supported(s, Cout) && s.H == H && s.W == W && s.f32 && 9 * s.C <= 32 &&
+           conv_first_wgrad_stream_ok(s, N, H, W, 2) && !(g_debug_flags & (1 << 28));
+}
+int conv_first_wgrad_bn(const ustrun_src_t& s, const void* da, const void* y, const float* scale, const float* shift, const float* coef,
+                        int gN, long aff_stride, int N, float* dw, int accumulate, float* partials, int64_t partials_bytes,
+                        hipStream_t st) {
+    USTRUN_CHECK(da && y && scale && shift && coef && dw && partials, "conv_first_wgrad_bn: null pointer");
+    USTRUN_CHECK(partials_bytes >= conv_first_wgrad_partials_bytes(), "conv_first_wgrad_bn: partials too small");
+    USTRUN_CHECK(conv_first_wgrad_bn_ok(s, N, s.H, s.W, 64, USTRUN_D16), "conv_first_wgrad_bn: layout outside the streaming kernel's range");
+    USTRUN_CHECK(gN >= 1 && aff_stride % 4 == 0 && !(((uintptr_t)scale | (uintptr_t)shift | (uintptr_t)coef) & 15),
+                 "conv_first_wgrad_bn: constants must be 16-byte aligned, gN=%d", gN);
+    const CfWgradBn bn = {y, scale, shift, coef, gN, (int)aff_stride, 3 * 64};
+    return launch_wgrad_stream<WgOp16Bn>(s, da, N, dw, accumulate, partials, st, bn);
 }
 
 }  // namespace ustrun

@@ -210,7 +210,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
         const long g = blockIdx.y;
         dl += g * npix * K;
         y = (const float*)((const char*)y + g * npix * C * ESZ);
-        da = (float*)((char*)da + g * npix * C * ESZ);
+        if (da) da = (float*)((char*)da + g * npix * C * ESZ);
         if (scale) { scale += g * pass_aff; shift += g * pass_aff; }
         partials += g * (long)gridDim.x * (K * C + K + (bnr ? 2 * C : 0));
     }
@@ -235,27 +235,32 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
         for (int k = 0; k < KN; ++k) wk[k] = (k < K) ? *(const f32x4*)(w + k * C + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
         f32x4 scv = {1.f, 1.f, 1.f, 1.f}, shv = {0.f, 0.f, 0.f, 0.f};
         if (scale && active) { scv = *(const f32x4*)(scale + c); shv = *(const f32x4*)(shift + c); }
-        if (active)
-            for (long p = (long)blockIdx.x * PPB + pl; p < npix; p += (long)gridDim.x * PPB) {
+        if (active) {
+            // One pixel per trip left a lane's 8-byte load of y and its dl values as the only bytes in flight -- 16 waves per CU: the
+            // kernel ran at the memory latency, 2.6 TB/s.  U pixels' loads are issued before the first is used; the pixels are then
+            // taken in the same ascending order, so every sum is formed exactly as before.
+            constexpr int U = KT == 2 ? 3 : (KT == 4 ? 2 : 1);
+            const long S = (long)gridDim.x * PPB;
+            auto fetch = [&](long p, f32x4& yv, float (&d)[KN]) {
                 const long n = (unsigned)p / (unsigned)HW, hw = p - n * HW;   // 32-bit divide: p < 2^32 (checked on the host)
-                f32x4 a = ld4t<ESZ>(y, p * C + c);
-                const f32x4 yraw = a;
-                float d[KN];
+                yv = ld4t<ESZ>(y, p * C + c);
 #pragma unroll
                 for (int k = 0; k < KN; ++k) d[k] = (KT > 0 || k < K) ? dl[(n * K + k) * HW + hw] : 0.f;
+            };
+            auto pixel = [&](long p, f32x4 a, const float (&d)[KN]) {
+                const f32x4 yraw = a;
                 if (scale) {
                     a = a * scv + shv;
                     a[0] = fmaxf(a[0], 0.f); a[1] = fmaxf(a[1], 0.f); a[2] = fmaxf(a[2], 0.f); a[3] = fmaxf(a[3], 0.f);
                 }
-                f32x4 g = {0.f, 0.f, 0.f, 0.f};
+                f32x4 g = head_grad4<KN, KT == 0>(d, wk, K);
 #pragma unroll
                 for (int k = 0; k < KN; ++k)
                     if (KT > 0 || k < K) {
-                        g += d[k] * wk[k];
                         dwp[k] += d[k] * a;
                         dbp[k] += d[k];
                     }
-                st4t<ESZ>(da, p * C + c, g);
+                if (da) st4t<ESZ>(da, p * C + c, g);          // (null: layer 17's apply pass forms g again from dl, nobody else reads it)
                 if (bnr) {                                   // on the values as stored (what a reduce pass would read back)
                     if (ESZ == 2) { g[0] = (float)(elt_t)g[0]; g[1] = (float)(elt_t)g[1]; g[2] = (float)(elt_t)g[2]; g[3] = (float)(elt_t)g[3]; }
 #pragma unroll
@@ -264,7 +269,21 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
                         bs1[q] += dz; bs2[q] += dz * yraw[q];
                     }
                 }
+            };
+            long p = (long)blockIdx.x * PPB + pl;
+            for (; p + (U - 1) * S < npix; p += U * S) {
+                f32x4 yv[U]; float d[U][KN];
+#pragma unroll
+                for (int u = 0; u < U; ++u) fetch(p + u * S, yv[u], d[u]);
+#pragma unroll
+                for (int u = 0; u < U; ++u) pixel(p + u * S, yv[u], d[u]);
             }
+            for (; p < npix; p += S) {
+                f32x4 yv; float d[KN];
+                fetch(p, yv, d);
+                pixel(p, yv, d);
+            }
+        }
         // fixed-order block reduction over the PPB pixel lanes, one class at a time
         for (int k = 0; k < K; ++k) {
             f32x4 v = dwp[0]; float b = dbp[0];
@@ -393,7 +412,7 @@ int head_bwd_passes(const float* dlogits, const void* y, const float* scale, con
                     int K, const float* w, void* da, float* dw, float* db, int accumulate, float* partials,
                     int64_t partials_bytes, int dtype, int passes, long pass_aff, hipStream_t s, int* bn_rows) {
     USTRUN_CHECK(dtype_ok(dtype), "head_bwd: dtype %d not built", dtype);
-    USTRUN_CHECK(dlogits && y && w && da && dw && db && partials, "head_bwd: null pointer");
+    USTRUN_CHECK(dlogits && y && w && dw && db && partials, "head_bwd: null pointer");        // (da null: the gradient is not stored)
     USTRUN_CHECK(C % 4 == 0 && C > 0 && K >= 1 && K <= KMAX, "head_bwd: C=%d K=%d unsupported", C, K);
     USTRUN_CHECK(npix > 0 && HW > 0 && npix < (1LL << 32) && passes >= 1, "head_bwd: bad extent");
     const int LPP = lanes_per_pixel(C / 4);
@@ -425,6 +444,7 @@ int head_bwd_passes(const float* dlogits, const void* y, const float* scale, con
 extern "C" int ustrun_head_bwd(const float* dlogits, const void* y, const float* scale, const float* shift,
                                int64_t npix, int HW, int C, int K, const float* w, void* da, float* dw, float* db,
                                int accumulate, float* partials, int64_t partials_bytes, int dtype, ustrun_stream_t s) {
+    USTRUN_CHECK(da, "head_bwd: null pointer");
     return head_bwd_passes(dlogits, y, scale, shift, npix, HW, C, K, w, da, dw, db, accumulate, partials, partials_bytes, dtype, 1,
                            0, (hipStream_t)s, nullptr);
 }

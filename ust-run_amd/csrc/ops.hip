@@ -499,6 +499,16 @@ extern "C" int ustrun_conv3x3_wgrad(const ustrun_src_t* srcs, int nsrc, const vo
     return reduce_partials(partials, slabs, 9, a.Cin, Cout, dw, 0, accumulate, (hipStream_t)s);
 }
 
+extern "C" int ustrun_conv_first_wgrad_bn(const ustrun_src_t* src, const void* da, const void* y, const float* scale, const float* shift,
+                                          const float* coef, int gN, int64_t aff_stride, int N, int H, int W, int Cout, float* dw,
+                                          int accumulate, float* partials, int64_t partials_bytes, int dtype, ustrun_stream_t s) {
+    USTRUN_TRY(check_srcs(src, 1, "conv_first_wgrad_bn"));
+    USTRUN_CHECK(N > 0 && H > 0 && W > 0, "conv_first_wgrad_bn: bad args");
+    USTRUN_CHECK(conv_first_wgrad_bn_ok(*src, N, H, W, Cout, dtype), "conv_first_wgrad_bn: shape or dtype not served");
+    return conv_first_wgrad_bn(*src, da, y, scale, shift, coef, gN > 0 ? gN : N, (long)aff_stride, N, dw, accumulate, partials,
+                               partials_bytes, (hipStream_t)s);
+}
+
 namespace ustrun {
 namespace {
 // db[co] = sum over all pixels of du[p][co]: block partials then reduce_rows.  thread = (4-channel group,

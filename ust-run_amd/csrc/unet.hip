@@ -400,6 +400,11 @@ extern "C" int ustrun_unet_backward(const ustrun_unet_desc_t* d, const float* x,
     return ustrun_unet_backward_part(d, x, dlogits, workspace, scratch, grads, accumulate, 0, s);
 }
 
+// ustrun_debug_last_backward_route: bit 0 = layer 17's da formed from dlogits in its apply pass, bit 1 = layer 0's apply pass inside
+// the first convolution's weight gradient; per calling thread, reset by every backward call
+static thread_local int g_last_backward_route = 0;
+extern "C" int ustrun_debug_last_backward_route(void) { return g_last_backward_route; }
+
 // part 0: everything; part 1: head + decoder (the gradients of up1..up4 and outc, the contiguous tail of the parameter
 // order, are final afterwards); part 2: encoder, continuing from the same scratch -- or, finer, part 3: down4 (its
 // gradients are final afterwards) then part 4: down3..inc.  Lets the caller start the all-reduce of the decoder gradients
@@ -434,16 +439,27 @@ extern "C" int ustrun_unet_backward_io(const ustrun_unet_desc_t* d, const float*
     if (dfeat) dfeat += (long)p.ob * p.base * p.H * p.W;
     const int dt = d->dtype;
 
+    g_last_backward_route = 0;
+    // ustrun_debug_flags2 bit 4: both full-resolution round trips stay (da17 stored and read back, dy0 written and read back);
+    // bit 5: layer 17's alone, bit 6: layer 0's alone (each half measured with the other in place)
+    const bool keep17 = (g_debug_flags2 & (16 | 32)) != 0, keep0 = (g_debug_flags2 & (16 | 64)) != 0;
     int head_bn_rows = 0;       // > 0: the head kernel also formed layer 17's BatchNorm-backward sums (rows per pass, in `part`)
+    bool da17_from_dl = false;  // the head stored no da17: layer 17's apply pass forms it again from dlogits (bn_bwd_apply_head_passes)
     if (which <= 1) {   // head: all passes in one launch (blockIdx.y = pass: its BatchNorm constants on load)
         const int C = p.cout[17];
         const long gpix = (long)p.gN * p.H * p.W;
+        // With K classes da17 is K multiply-adds on 4 K bytes of dlogits per pixel: cheaper to form twice than to store (128 B per
+        // pixel) and load once.  Its only other reader would be the reduce pass, so the head must have formed the sums itself.
+        const bool sums_in_head = !(g_debug_flags & 8388608) && !dfeat;
+        // (not with the stop-early aid of bits 16-20, whose users read da17 from the scratch)
+        da17_from_dl = !keep17 && dlogits && sums_in_head && dt == USTRUN_D16 && bn_bwd_apply_head_ok(C, p.K, dt) &&
+                       gpix < (1L << 31) && !((g_debug_flags >> 16) & 31);
         // (with dfeat the head's fused sums would miss it: the head runs without them -- the route bit 23 takes -- and layer 17's
         // BatchNorm backward runs its reduce pass over the summed da)
         if (dlogits)
         USTRUN_TRY(head_bwd_passes(dlogits, yb(17), affp(17), affp(17) + C, gpix, p.H * p.W, C, p.K, d->head_w,
-                                   sc + p.da_off[17], grads[p.gi_head], grads[p.gi_head + 1], accumulate, part, p.part_bytes, dt, p.Gb, 4L * C,
-                                   (hipStream_t)s, ((g_debug_flags & 8388608) || dfeat) ? nullptr : &head_bn_rows));
+                                   da17_from_dl ? nullptr : sc + p.da_off[17], grads[p.gi_head], grads[p.gi_head + 1], accumulate, part,
+                                   p.part_bytes, dt, p.Gb, 4L * C, (hipStream_t)s, sums_in_head ? &head_bn_rows : nullptr));
         else if (!accumulate) {     // no gradient at the logits: the head's parameters get zeros
             hipError_t e = hipMemsetAsync(grads[p.gi_head], 0, sizeof(float) * p.K * C, (hipStream_t)s);
             if (e == hipSuccess) e = hipMemsetAsync(grads[p.gi_head + 1], 0, sizeof(float) * p.K, (hipStream_t)s);
@@ -465,6 +481,12 @@ extern "C" int ustrun_unet_backward_io(const ustrun_unet_desc_t* d, const float*
         const bool pooled = (i < 8) && (i % 2 == 1);
         const void* dp = pooled ? sc + p.dp_off[3 - l] : nullptr;
         void* da = sc + p.da_off[i];
+        ustrun_src_t srcs[2];
+        const int ns = conv_sources(p, x, ws, i, srcs, true);
+        // Layer 0 without dx: dy0's only reader is the first convolution's weight gradient, which then forms it from da0 and y0 in its
+        // loader (conv_first_wgrad_bn) -- no apply pass, no dy0 written and read back.  conv_first_dgrad needs the stored dy0.
+        const bool dy0_on_load = i == 0 && !keep0 && !dx && dt == USTRUN_D16 && ns == 1 &&
+                                 conv_first_wgrad_bn_ok(srcs[0], p.Nb, H, W, C, dt) && !((g_debug_flags >> 16) & 31);
         {   // BatchNorm backward is a per-pass reduction: all passes in one launch per kernel (blockIdx.y = pass)
             const long act = (long)p.gN * H * W * C, pl = (long)p.gN * (H / 2) * (W / 2) * C;
             if (i == 17 && head_bn_rows > 0) {      // the sums came with the head's partial rows: no reduce pass over da and y
@@ -480,15 +502,27 @@ extern "C" int ustrun_unet_backward_io(const ustrun_unet_desc_t* d, const float*
             USTRUN_TRY(bn_bwd_reduce_passes(da, dp, yb(i), aff, aff + C, aff + 2 * C, aff + 3 * C, d->bn_w[i], p.gN, H, W,
                                             C, grads[gi + 1], grads[gi + 2], accumulate, coef, part, p.part_bytes, dt, p.Gb, act,
                                             pl, 4L * C, (hipStream_t)s));
+            if (i == 17 && da17_from_dl) {
+                USTRUN_CHECK(head_bn_rows > 0, "unet_backward: the head formed no BatchNorm-backward sums");
+                USTRUN_TRY(bn_bwd_apply_head_passes(dlogits, d->head_w, yb(i), aff, aff + C, coef, p.gN, H, W, C, p.K, da, dt, p.Gb, act,
+                                                    4L * C, (hipStream_t)s));
+                g_last_backward_route |= 1;
+            } else if (!dy0_on_load)
             USTRUN_TRY(bn_bwd_apply_passes(da, dp, yb(i), aff, aff + C, coef, p.gN, H, W, C, da, dt, p.Gb, act, pl,
                                            4L * C, (hipStream_t)s));
         }
         dgrad_bn_rows = 0;
-        ustrun_src_t srcs[2];
-        const int ns = conv_sources(p, x, ws, i, srcs, true);
         prof_set_tag(200 + i, p.Nb);
+        if (dy0_on_load) {
+            const int rc = conv_first_wgrad_bn(srcs[0], da, yb(0), aff, aff + C, coef, p.gN, 4L * C, p.Nb, grads[gi], accumulate, part,
+                                               p.part_bytes, (hipStream_t)s);
+            prof_set_tag(-1, 0);
+            USTRUN_TRY(rc);
+            g_last_backward_route |= 2;
+        } else {
         USTRUN_TRY(ustrun_conv3x3_wgrad(srcs, ns, da, p.Nb, H, W, C, grads[gi], accumulate, part, p.part_bytes, dt, s));
         prof_set_tag(-1, 0);
+        }
         if (i == 0) {
             if (dx) {       // the network input's gradient: zero for the leading passes and the tail pass, which get none
                 const long img = (long)p.C * p.H * p.W;

@@ -69,12 +69,14 @@ SIGNATURES = {
     "ustrun_bn_bwd_partials_bytes": (i64, [i64, i32]),
     "ustrun_bn_bwd_reduce": (i32, [vp, vp, vp, fp, fp, fp, fp, fp, i32, i32, i32, i32, fp, fp, i32, fp, fp, i64, i32, vp]),
     "ustrun_bn_bwd_apply": (i32, [vp, vp, vp, fp, fp, fp, i32, i32, i32, i32, vp, i32, vp]),
+    "ustrun_bn_bwd_apply_head": (i32, [fp, fp, vp, fp, fp, fp, i32, i32, i32, i32, i32, vp, i32, i32, i64, vp]),
     "ustrun_conv3x3_dgrad": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "ustrun_conv3x3_dgrad_bnsum": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, fp, fp, i32, i64, fp, C.POINTER(i32), i32, vp]),
     "ustrun_bn_bwd_finalize_stat": (i32, [fp, i32, i32, i32, i64, fp, fp, fp, i64, fp, fp, i32, fp, vp]),
     "ustrun_convT2x2_dgrad_bnsum": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, fp, fp, i32, i64, fp, C.POINTER(i32), i32, vp]),
     "ustrun_wgrad_partials_bytes": (i64, [i32, i32, i32, i64]),
     "ustrun_conv3x3_wgrad": (i32, [PSrc, i32, vp, i32, i32, i32, i32, fp, i32, fp, i64, i32, vp]),
+    "ustrun_conv_first_wgrad_bn": (i32, [PSrc, vp, vp, fp, fp, fp, i32, i64, i32, i32, i32, i32, fp, i32, fp, i64, i32, vp]),
     "ustrun_convT2x2_dgrad": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp]),
     "ustrun_convT2x2_wgrad": (i32, [PSrc, vp, i32, i32, i32, i32, fp, fp, i32, fp, i64, i32, vp]),
     "ustrun_pseudo_label": (i32, [fp, i32, i32, i32, f32, i32, vp, fp, vp]),
@@ -133,6 +135,7 @@ SIGNATURES = {
     "ustrun_short_last_pass": (i32, [i32]),
     "ustrun_debug_buffer": (i32, [vp, i64]),
     "ustrun_debug_last_bn_variant": (i32, []),
+    "ustrun_debug_last_backward_route": (i32, []),
     "ustrun_debug_clock_probe": (i32, [vp, i32, vp]),
     "ustrun_profile_enable": (i32, [i32]),
     "ustrun_profile_collect": (i32, [i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64)]),
