@@ -316,6 +316,78 @@ int ustrun_dice_bwd(const float* logits, const void* target, int target_is_i64, 
                     int mask_per_pixel, int N, int K, int HW, int act, int multi, const float* weight_host, const float* sums,
                     const float* gscale_dev, float gscale, float* dlogits, ustrun_stream_t s);
 
+/* ... the same pair with the Dice smoothing term as an argument (ustrun_dice_* hard-wire DiceLossWithMask's 1e-10): DiceLoss of
+ * utils/losses.py:156-192 is the per-class form with smooth = 1e-5, no mask.                                            */
+int ustrun_dice_smooth_fwd(const float* logits, const void* target, int target_is_i64, int target_per_pixel, const float* mask,
+                           int mask_per_pixel, int N, int K, int HW, int act, int multi, const float* weight_host, float smooth,
+                           float* out, float* partials, int64_t partials_bytes, ustrun_stream_t s);
+int ustrun_dice_smooth_bwd(const float* logits, const void* target, int target_is_i64, int target_per_pixel, const float* mask,
+                           int mask_per_pixel, int N, int K, int HW, int act, int multi, const float* weight_host, float smooth,
+                           const float* sums, const float* gscale_dev, float gscale, float* dlogits, ustrun_stream_t s);
+
+/* ---- the semi-supervised loss toolkit of utils/losses.py (csrc/consistency.hip) ------------------------------------------
+ * Operands are f32 NCHW [N,K,HW], K = 1..8; softmax / sigmoid run across the K planes of a pixel.  A lane takes four consecutive
+ * pixels with 16-byte accesses when HW % 4 == 0 and every pointer is 16-byte aligned, one pixel otherwise (same arithmetic).
+ * Scalar results are device floats; reductions are block partial rows (partials: ustrun_loss_partials_bytes) added in a fixed
+ * order in double by one block, no floating-point atomics: a repeated call is bit-identical.  Every backward takes the upstream
+ * gradient as a DEVICE pointer (gout_dev: one float for a scalar result, the map for a map result) and recomputes the
+ * probabilities from its inputs.
+ *
+ * Pair consistency between two logit tensors a, b (act: USTRUN_LOSS_SOFTMAX / USTRUN_LOSS_SIGMOID; pa, pb the probabilities):
+ *   USTRUN_CONS_MSE_MAP   out[N,K,HW] = (pa - pb)^2                                        softmax_mse_loss, losses.py:65-82
+ *   USTRUN_CONS_KL_MEAN   out[0] = mean over N*K*HW of pb (log pb - log pa), both logs from the log-softmax / log-sigmoid of the
+ *                         logits (a term is 0 where pb is 0)                                softmax_kl_loss, losses.py:85-104
+ *   USTRUN_CONS_SOFT_DICE out[0] = mean_k 1 - (2 sum pa_k pb_k + 1e-5) / (sum pa_k + sum pb_k + 1e-5), the sums NOT squared
+ *                         (dice_loss1)                                                      softmax_dice_loss, losses.py:39-56
+ * Scalar kinds: out holds USTRUN_CONS_NOUT floats (out[0] the loss, behind it the per-class sums the backward reads as `sums`).
+ * bwd writes da and / or db (NULL skips a side), each through its own softmax / sigmoid Jacobian.                       */
+enum { USTRUN_CONS_MSE_MAP = 0, USTRUN_CONS_KL_MEAN = 1, USTRUN_CONS_SOFT_DICE = 2 };
+#define USTRUN_CONS_NOUT 25
+int ustrun_consistency_fwd(const float* a, const float* b, int N, int K, int HW, int act, int kind, float* out, float* partials,
+                           int64_t partials_bytes, ustrun_stream_t s);
+int ustrun_consistency_bwd(const float* a, const float* b, int N, int K, int HW, int act, int kind, const float* sums,
+                           const float* gout_dev, float* da, float* db, ustrun_stream_t s);
+
+/* Entropy of a probability map p [N,K,HW]: e = -factor sum_k p_k log(p_k + 1e-6) per pixel (factor 1: entropy_minmization /
+ * entropy_map, losses.py:271-281; factor 1/ln C: entropy_loss / entropy_loss_map, :30-36,59-62).  mean = 0: out is the map
+ * [N,1,HW], gout_dev a map of that shape; mean = 1: out[0] is the mean over N*HW.
+ * bwd: dp_k = -(log(p_k + 1e-6) + p_k / (p_k + 1e-6)) * factor * upstream.                                             */
+int ustrun_entropy_fwd(const float* p, int N, int K, int HW, float factor, int mean, float* out, float* partials,
+                       int64_t partials_bytes, ustrun_stream_t s);
+int ustrun_entropy_bwd(const float* p, int N, int K, int HW, float factor, int mean, const float* gout_dev, float* dp,
+                       ustrun_stream_t s);
+
+/* FocalLoss.forward (losses.py:130-153): logits [N,K,HW], target int64 [N,HW]; per pixel -(1 - pt)^gamma alpha_t log pt with pt
+ * the softmax probability of the target class, alpha_host = K host floats or NULL (no alpha); out[0] = the mean (mean = 1) or
+ * the sum over N*HW.  A target outside [0,K) contributes nothing.
+ * The reference DETACHES pt inside the modulating factor (losses.py:141: Variable(logpt.data.exp())), so bwd writes
+ *   dlogits_k = (1 - pt)^gamma alpha_t (p_k - [k = t]) * upstream (/ N*HW for the mean)
+ * with no derivative of (1 - pt)^gamma.  That is the reference's gradient, kept on purpose.                             */
+int ustrun_focal_fwd(const float* logits, const int64_t* target, int N, int K, int HW, float gamma, const float* alpha_host,
+                     int mean, float* out, float* partials, int64_t partials_bytes, ustrun_stream_t s);
+int ustrun_focal_bwd(const float* logits, const int64_t* target, int N, int K, int HW, float gamma, const float* alpha_host,
+                     int mean, const float* gout_dev, float* dlogits, ustrun_stream_t s);
+
+/* Six sums over two flat f32 arrays of n elements in one pass, and the three scalar losses built on them:
+ *   out[0..5] = sum ab, sum a^2, sum b^2, sum a, sum b, sum (a-b)^2
+ *   out[6] = 1 - (2 sum ab + 1e-5) / (sum a^2 + sum b^2 + 1e-5)     dice_loss, losses.py:8-16        (USTRUN_PAIR_DICE_SQ)
+ *   out[7] = 1 - (2 sum ab + 1e-5) / (sum a + sum b + 1e-5)         dice_loss1, losses.py:19-27      (USTRUN_PAIR_DICE)
+ *   out[8] = sum (a-b)^2 / n                                        symmetric_mse_loss, :107-116     (USTRUN_PAIR_MSE)
+ * (USTRUN_PAIR_NOUT floats).  bwd: the gradient of loss `kind` times gout_dev[0] into da and / or db (NULL skips a side).  */
+enum { USTRUN_PAIR_DICE_SQ = 0, USTRUN_PAIR_DICE = 1, USTRUN_PAIR_MSE = 2 };
+#define USTRUN_PAIR_NOUT 9
+int ustrun_pair_sums(const float* a, const float* b, int64_t n, float* out, float* partials, int64_t partials_bytes,
+                     ustrun_stream_t s);
+int ustrun_pair_sums_bwd(const float* a, const float* b, int64_t n, int kind, const float* sums, const float* gout_dev,
+                         float* da, float* db, ustrun_stream_t s);
+
+/* compute_kl_loss (losses.py:284-295) on a, b viewed as [rows, C] with the softmax over the C contiguous values of a row, any C:
+ * out[0] = (mean pb (log pb - log pa) + mean pa (log pa - log pb)) / 2, the means over rows*C.  One lane per row: not a hot path. */
+int ustrun_row_kl_fwd(const float* a, const float* b, int64_t rows, int C, float* out, float* partials, int64_t partials_bytes,
+                      ustrun_stream_t s);
+int ustrun_row_kl_bwd(const float* a, const float* b, int64_t rows, int C, const float* gout_dev, float* da, float* db,
+                      ustrun_stream_t s);
+
 /* ---- per-sample binary overlap counts for the numpy Dice of utils/metrics.py:114-146 ---------
  * counts[n][c] = {|pred|, |gt|, |pred & gt|} with pred/gt binarised as (x == cls[c]) or (x != 0). */
 int ustrun_dice_counts(const void* pred, const void* gt, int pred_is_i64, int gt_is_i64, int N,

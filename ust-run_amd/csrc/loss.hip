@@ -2,21 +2,13 @@
 // the pseudo-label / target-mixing streams.  Everything is HBM-bound: one lane per pixel reads the
 // K logit planes (NCHW: coalesced per plane), reductions go wavefront shuffle -> LDS -> one
 // partial row per block -> single-block f64 finalize (fixed order: reproducible).
-#include "common.h"
+#include "stream_reduce.h"
 #include <cstring>
 
 namespace ustrun {
 namespace {
 
-constexpr int KMAX = 8;
-constexpr int NS = 1 + 3 * KMAX;   // per-thread running sums: ce, I[k], Z[k], Y[k]
 constexpr float SMOOTH = 1e-10f;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // softmax mode: target int64 [N,HW], mask f32 [N,HW] or null.  sigmoid mode: target/mask f32 [N,K,HW].
 __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float* __restrict__ logits, const void* __restrict__ target,
@@ -376,20 +368,13 @@ __global__ void amp_update_kernel(float* __restrict__ state, float growth, float
     state[0] = scale; state[1] = scale; state[2] = tracker; state[3] = 0.f;
 }
 
-int stream_blocks(long work_items) {
-    long b = (work_items + 256 * 4 - 1) / (256 * 4);
-    if (b > 1024) b = 1024;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 // ---- DiceLossWithMask.forward in EVERY mode combination (utils/losses.py:236-268): the two the step uses run fused with their
 // CE / BCE terms above; this pair serves the rest of the reference signature (class weights, sigmoid per class, softmax + multi,
 // raw inputs).  One lane per pixel, all K classes of the pixel in registers.
 //   act: 0 none, 1 softmax over classes, 2 sigmoid          multi: one global Dice over [N,K,HW] instead of per class
 //   per class: t_k = (target == k) from a class-index map [N,HW] (int64 or f32), m_k = 1 for k = 0, (mask == 1) for k >= 1 (Q4)
 //   multi:     t, m elementwise f32 [N,K,HW], or [N,HW] broadcast over the classes (tper / mper = 1)
-struct DiceCfg { int N, K, HW, act, multi, t_i64, tper, mper; float w[KMAX]; };
+struct DiceCfg { int N, K, HW, act, multi, t_i64, tper, mper; float w[KMAX]; float smooth; };      // smooth: SMOOTH for DiceLossWithMask, 1e-5 for DiceLoss
 
 __device__ __forceinline__ void dice_pixel(const DiceCfg& c, const float* __restrict__ logits, const void* __restrict__ target,
                                            const float* __restrict__ mask, long n, long hw, long p, float* pk, float* tk, float* mk) {
@@ -471,12 +456,12 @@ __global__ void dice_finalize_kernel(const DiceCfg c, const float* __restrict__ 
         if (c.multi) {
             double I = 0, Z = 0, Y = 0;
             for (int k = 0; k < c.K; ++k) { I += tot[1 + k]; Z += tot[1 + KMAX + k]; Y += tot[1 + 2 * KMAX + k]; }
-            loss = 1.0 - (2.0 * I + (double)SMOOTH) / (Z + Y + (double)SMOOTH);
+            loss = 1.0 - (2.0 * I + (double)c.smooth) / (Z + Y + (double)c.smooth);
             for (int k = 0; k < c.K; ++k) { out[1 + k] = k ? 0.f : (float)I; out[1 + c.K + k] = k ? 0.f : (float)Z; out[1 + 2 * c.K + k] = k ? 0.f : (float)Y; }
         } else {
             for (int k = 0; k < c.K; ++k) {
                 const double I = tot[1 + k], Z = tot[1 + KMAX + k], Y = tot[1 + 2 * KMAX + k];
-                loss += (double)c.w[k] * (1.0 - (2.0 * I + (double)SMOOTH) / (Z + Y + (double)SMOOTH));
+                loss += (double)c.w[k] * (1.0 - (2.0 * I + (double)c.smooth) / (Z + Y + (double)c.smooth));
                 out[1 + k] = (float)I; out[1 + c.K + k] = (float)Z; out[1 + 2 * c.K + k] = (float)Y;
             }
             loss /= c.K;
@@ -494,10 +479,10 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const DiceCfg c, const fl
     for (int k = 0; k < KMAX; ++k)
         if (k < c.K) {
             const int kk = c.multi ? 0 : k;
-            const float I = sums[1 + kk], D = sums[1 + c.K + kk] + sums[1 + 2 * c.K + kk] + SMOOTH;
+            const float I = sums[1 + kk], D = sums[1 + c.K + kk] + sums[1 + 2 * c.K + kk] + c.smooth;
             const float wk = c.multi ? 1.f : c.w[k] / c.K;
             A[k] = -2.f / D * wk;
-            Bc[k] = 2.f * (2.f * I + SMOOTH) / (D * D) * wk;
+            Bc[k] = 2.f * (2.f * I + c.smooth) / (D * D) * wk;
         }
     const long npix = (long)c.N * c.HW;
     for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
@@ -561,22 +546,24 @@ extern "C" int ustrun_seg_loss_bwd(const float* logits, const void* target, cons
 
 
 static int dice_cfg(DiceCfg* c, const char* who, const void* logits, const void* target, int N, int K, int HW, int act, int multi,
-                    int target_is_i64, int target_per_pixel, int mask_per_pixel, const float* weight_host) {
+                    int target_is_i64, int target_per_pixel, int mask_per_pixel, const float* weight_host, float smooth) {
     USTRUN_CHECK(logits && target, "%s: null pointer", who);
+    USTRUN_CHECK(smooth >= 0.f, "%s: smooth %g", who, (double)smooth);
     USTRUN_CHECK(K >= 1 && K <= KMAX && N > 0 && HW > 0 && (long)N * HW < (1L << 32), "%s: bad shape N=%d K=%d HW=%d", who, N, K, HW);
     USTRUN_CHECK(act >= 0 && act <= 2, "%s: activation %d (0 none, 1 softmax, 2 sigmoid)", who, act);
     USTRUN_CHECK(multi || target_per_pixel, "%s: the per-class form takes a class-index target [N,HW]", who);
     USTRUN_CHECK(!multi || !target_is_i64, "%s: the multi form takes float targets", who);
     c->N = N; c->K = K; c->HW = HW; c->act = act; c->multi = multi; c->t_i64 = target_is_i64; c->tper = target_per_pixel; c->mper = mask_per_pixel;
     for (int k = 0; k < KMAX; ++k) c->w[k] = (weight_host && k < K) ? weight_host[k] : 1.f;
+    c->smooth = smooth;
     return 0;
 }
 
-extern "C" int ustrun_dice_fwd(const float* logits, const void* target, int target_is_i64, int target_per_pixel, const float* mask,
-                               int mask_per_pixel, int N, int K, int HW, int act, int multi, const float* weight_host, float* out,
-                               float* partials, int64_t partials_bytes, ustrun_stream_t s) {
+extern "C" int ustrun_dice_smooth_fwd(const float* logits, const void* target, int target_is_i64, int target_per_pixel, const float* mask,
+                                      int mask_per_pixel, int N, int K, int HW, int act, int multi, const float* weight_host, float smooth,
+                                      float* out, float* partials, int64_t partials_bytes, ustrun_stream_t s) {
     DiceCfg c;
-    USTRUN_TRY(dice_cfg(&c, "dice_fwd", logits, target, N, K, HW, act, multi, target_is_i64, target_per_pixel, mask_per_pixel, weight_host));
+    USTRUN_TRY(dice_cfg(&c, "dice_fwd", logits, target, N, K, HW, act, multi, target_is_i64, target_per_pixel, mask_per_pixel, weight_host, smooth));
     USTRUN_CHECK(out && partials && partials_bytes >= ustrun_loss_partials_bytes(N, K, HW), "dice_fwd: partials too small");
     const int blocks = stream_blocks((long)N * HW);
     hipLaunchKernelGGL(dice_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)s, c, logits, target, mask, partials);
@@ -586,16 +573,30 @@ extern "C" int ustrun_dice_fwd(const float* logits, const void* target, int targ
     return 0;
 }
 
-extern "C" int ustrun_dice_bwd(const float* logits, const void* target, int target_is_i64, int target_per_pixel, const float* mask,
-                               int mask_per_pixel, int N, int K, int HW, int act, int multi, const float* weight_host, const float* sums,
-                               const float* gscale_dev, float gscale, float* dlogits, ustrun_stream_t s) {
+extern "C" int ustrun_dice_smooth_bwd(const float* logits, const void* target, int target_is_i64, int target_per_pixel, const float* mask,
+                                      int mask_per_pixel, int N, int K, int HW, int act, int multi, const float* weight_host, float smooth,
+                                      const float* sums, const float* gscale_dev, float gscale, float* dlogits, ustrun_stream_t s) {
     DiceCfg c;
-    USTRUN_TRY(dice_cfg(&c, "dice_bwd", logits, target, N, K, HW, act, multi, target_is_i64, target_per_pixel, mask_per_pixel, weight_host));
+    USTRUN_TRY(dice_cfg(&c, "dice_bwd", logits, target, N, K, HW, act, multi, target_is_i64, target_per_pixel, mask_per_pixel, weight_host, smooth));
     USTRUN_CHECK(sums && dlogits, "dice_bwd: null pointer");
     hipLaunchKernelGGL(dice_bwd_kernel, dim3(stream_blocks((long)N * HW)), dim3(256), 0, (hipStream_t)s, c, logits, target, mask, sums,
                        gscale_dev, gscale, dlogits);
     USTRUN_LAUNCH_CHECK("dice_bwd");
     return 0;
+}
+
+extern "C" int ustrun_dice_fwd(const float* logits, const void* target, int target_is_i64, int target_per_pixel, const float* mask,
+                               int mask_per_pixel, int N, int K, int HW, int act, int multi, const float* weight_host, float* out,
+                               float* partials, int64_t partials_bytes, ustrun_stream_t s) {
+    return ustrun_dice_smooth_fwd(logits, target, target_is_i64, target_per_pixel, mask, mask_per_pixel, N, K, HW, act, multi, weight_host,
+                                  SMOOTH, out, partials, partials_bytes, s);
+}
+
+extern "C" int ustrun_dice_bwd(const float* logits, const void* target, int target_is_i64, int target_per_pixel, const float* mask,
+                               int mask_per_pixel, int N, int K, int HW, int act, int multi, const float* weight_host, const float* sums,
+                               const float* gscale_dev, float gscale, float* dlogits, ustrun_stream_t s) {
+    return ustrun_dice_smooth_bwd(logits, target, target_is_i64, target_per_pixel, mask, mask_per_pixel, N, K, HW, act, multi, weight_host,
+                                  SMOOTH, sums, gscale_dev, gscale, dlogits, s);
 }
 
 extern "C" int ustrun_pseudo_label(const float* logits, int N, int K, int HW, float threshold, int mode, void* label,

@@ -10,6 +10,8 @@ LIB_PATH = os.environ.get("USTRUN_LIB", os.path.join(_HERE, "libustrun.so"))    
 
 F32, BF16, F16, F32X3 = 0, 1, 2, 3
 LOSS_SOFTMAX, LOSS_SIGMOID = 0, 1
+CONS_MSE_MAP, CONS_KL_MEAN, CONS_SOFT_DICE, CONS_NOUT = 0, 1, 2, 25
+PAIR_DICE_SQ, PAIR_DICE, PAIR_MSE, PAIR_NOUT = 0, 1, 2, 9
 
 vp, fp, i32, i64, f32 = C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -128,6 +130,18 @@ SIGNATURES = {
     "ustrun_debug_last_conv_variant": (i32, []),
     "ustrun_dice_fwd": (i32, [fp, vp, i32, i32, fp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_float), fp, fp, i64, vp]),
     "ustrun_dice_bwd": (i32, [fp, vp, i32, i32, fp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_float), fp, fp, f32, fp, vp]),
+    "ustrun_dice_smooth_fwd": (i32, [fp, vp, i32, i32, fp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_float), f32, fp, fp, i64, vp]),
+    "ustrun_dice_smooth_bwd": (i32, [fp, vp, i32, i32, fp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_float), f32, fp, fp, f32, fp, vp]),
+    "ustrun_consistency_fwd": (i32, [fp, fp, i32, i32, i32, i32, i32, fp, fp, i64, vp]),
+    "ustrun_consistency_bwd": (i32, [fp, fp, i32, i32, i32, i32, i32, fp, fp, fp, fp, vp]),
+    "ustrun_entropy_fwd": (i32, [fp, i32, i32, i32, f32, i32, fp, fp, i64, vp]),
+    "ustrun_entropy_bwd": (i32, [fp, i32, i32, i32, f32, i32, fp, fp, vp]),
+    "ustrun_focal_fwd": (i32, [fp, vp, i32, i32, i32, f32, C.POINTER(C.c_float), i32, fp, fp, i64, vp]),
+    "ustrun_focal_bwd": (i32, [fp, vp, i32, i32, i32, f32, C.POINTER(C.c_float), i32, fp, fp, vp]),
+    "ustrun_pair_sums": (i32, [fp, fp, i64, fp, fp, i64, vp]),
+    "ustrun_pair_sums_bwd": (i32, [fp, fp, i64, i32, fp, fp, fp, fp, vp]),
+    "ustrun_row_kl_fwd": (i32, [fp, fp, i64, i32, fp, fp, i64, vp]),
+    "ustrun_row_kl_bwd": (i32, [fp, fp, i64, i32, fp, fp, fp, vp]),
     "ustrun_debug_conv_stat_rows": (i32, [i32] * 10),
     "ustrun_debug_last_wgrad_variant": (i32, []),
     "ustrun_debug_flags": (i32, [i32]),

@@ -150,6 +150,239 @@ def dice_general(logits, target, mask=None, act="none", multi=False, weight=None
     return _DiceFn.apply(logits, target, mask, act, bool(multi), weight)
 
 
+# ---- the semi-supervised loss toolkit of utils/losses.py (csrc/consistency.hip) ----------------------------------------------------
+_CONS = {"mse_map": L.CONS_MSE_MAP, "kl_mean": L.CONS_KL_MEAN, "soft_dice": L.CONS_SOFT_DICE}
+_PAIR = {"dice_sq": L.PAIR_DICE_SQ, "dice": L.PAIR_DICE, "mse": L.PAIR_MSE}
+
+
+def _nkhw(t, name):
+    """[N,K,*] -> N, K, HW with every trailing dimension (3-D volumes too) flattened into HW"""
+    if t.dim() < 2:
+        raise RuntimeError(f"{name}: expected [N,K,...], got {tuple(t.shape)}")
+    N, K = t.shape[:2]
+    return N, K, t.numel() // max(1, N * K)
+
+
+def _partials(dev):
+    nb = L.lib().ustrun_loss_partials_bytes(1, 1, 1)
+    return torch.empty(nb // 4, dtype=torch.float32, device=dev), nb
+
+
+def _upstream(g):
+    return g.contiguous() if g.dtype == torch.float32 else g.float().contiguous()
+
+
+class _ConsFn(torch.autograd.Function):
+    """softmax_mse_loss / softmax_kl_loss / softmax_dice_loss (utils/losses.py:39-104) through ustrun_consistency_fwd/_bwd."""
+
+    @staticmethod
+    def forward(ctx, a, b, act, kind):
+        lib = L.lib()
+        a, b = _f32c(a, "input_logits"), _f32c(b, "target_logits")
+        assert a.size() == b.size()                                          # losses.py:47,73,93
+        N, K, HW = _nkhw(a, "input_logits")
+        if kind == "mse_map":
+            out, part, nb = torch.empty_like(a), None, 0
+        else:
+            out = torch.empty(L.CONS_NOUT, dtype=torch.float32, device=a.device)
+            part, nb = _partials(a.device)
+        L.check(lib.ustrun_consistency_fwd(a.data_ptr(), b.data_ptr(), N, K, HW, _MODE[act], _CONS[kind], out.data_ptr(), L.ptr(part), nb,
+                                           stream_ptr()), "ustrun_consistency_fwd")
+        ctx.save_for_backward(a, b) if kind == "mse_map" else ctx.save_for_backward(a, b, out)
+        ctx.cfg = (N, K, HW, act, kind)
+        return out if kind == "mse_map" else out[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        N, K, HW, act, kind = ctx.cfg
+        a, b = ctx.saved_tensors[:2]
+        sums = ctx.saved_tensors[2] if kind != "mse_map" else None
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        g = _upstream(g)
+        L.check(L.lib().ustrun_consistency_bwd(a.data_ptr(), b.data_ptr(), N, K, HW, _MODE[act], _CONS[kind], L.ptr(sums), g.data_ptr(),
+                                               L.ptr(da), L.ptr(db), stream_ptr()), "ustrun_consistency_bwd")
+        return da, db, None, None
+
+
+def consistency(a, b, act="softmax", kind="mse_map"):
+    """Pair consistency between two logit tensors [N,K,...], differentiable in both: kind "mse_map" -> the map (pa - pb)^2,
+    "kl_mean" -> mean pb (log pb - log pa) over every element, "soft_dice" -> the class mean of the unsquared soft Dice."""
+    return _ConsFn.apply(a, b, act, kind)
+
+
+class _EntropyFn(torch.autograd.Function):
+    """entropy_loss / entropy_loss_map / entropy_minmization / entropy_map (utils/losses.py:30-36,59-62,271-281)."""
+
+    @staticmethod
+    def forward(ctx, p, factor, mean):
+        p = _f32c(p, "p")
+        N, K, HW = _nkhw(p, "p")
+        if mean:
+            out = torch.empty(1, dtype=torch.float32, device=p.device)
+            part, nb = _partials(p.device)
+        else:
+            out, part, nb = torch.empty((N, 1) + tuple(p.shape[2:]), dtype=torch.float32, device=p.device), None, 0
+        L.check(L.lib().ustrun_entropy_fwd(p.data_ptr(), N, K, HW, factor, int(mean), out.data_ptr(), L.ptr(part), nb, stream_ptr()),
+                "ustrun_entropy_fwd")
+        ctx.save_for_backward(p)
+        ctx.cfg = (N, K, HW, factor, int(mean))
+        return out[0] if mean else out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        N, K, HW, factor, mean = ctx.cfg
+        p, = ctx.saved_tensors
+        dp, g = torch.empty_like(p), _upstream(g)
+        L.check(L.lib().ustrun_entropy_bwd(p.data_ptr(), N, K, HW, factor, mean, g.data_ptr(), dp.data_ptr(), stream_ptr()), "ustrun_entropy_bwd")
+        return dp, None, None
+
+
+def entropy(p, factor=1.0, mean=True):
+    """-factor sum_k p_k log(p_k + 1e-6) of a probability map [N,K,...]: the mean over the pixels, or the map [N,1,...]."""
+    return _EntropyFn.apply(p, float(factor), bool(mean))
+
+
+class _FocalFn(torch.autograd.Function):
+    """FocalLoss.forward (utils/losses.py:130-153); the modulating factor is a constant of the gradient, as there (:141)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, gamma, alpha, mean):
+        import ctypes as C
+        logits = _f32c(logits, "input")
+        N, K, HW = _nkhw(logits, "input")
+        if target.dtype != torch.int64 or not target.is_cuda or target.numel() != N * HW:
+            raise RuntimeError(f"FocalLoss target must be an int64 HIP tensor with N*H*W = {N * HW} elements, got {target.dtype} {tuple(target.shape)} on {target.device}")
+        target = target.contiguous()
+        if alpha is not None and len(alpha) < K:
+            raise IndexError("alpha needs one entry per class")           # (the reference's gather fails on a class beyond the table)
+        al = None if alpha is None else (C.c_float * K)(*[float(v) for v in alpha[:K]])
+        out = torch.empty(1, dtype=torch.float32, device=logits.device)
+        part, nb = _partials(logits.device)
+        L.check(L.lib().ustrun_focal_fwd(logits.data_ptr(), target.data_ptr(), N, K, HW, gamma, al, int(mean), out.data_ptr(), part.data_ptr(),
+                                         nb, stream_ptr()), "ustrun_focal_fwd")
+        ctx.save_for_backward(logits, target)
+        ctx.cfg = (N, K, HW, gamma, al, int(mean))
+        return out[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        N, K, HW, gamma, al, mean = ctx.cfg
+        logits, target = ctx.saved_tensors
+        dl, g = torch.empty_like(logits), _upstream(g)
+        L.check(L.lib().ustrun_focal_bwd(logits.data_ptr(), target.data_ptr(), N, K, HW, gamma, al, mean, g.data_ptr(), dl.data_ptr(),
+                                         stream_ptr()), "ustrun_focal_bwd")
+        return dl, None, None, None, None
+
+
+def focal(logits, target, gamma=2.0, alpha=None, mean=True):
+    """Focal loss of logits [N,K,...] (or [M,K]) against int64 class indices; alpha: a per-class sequence or None."""
+    return _FocalFn.apply(logits, target, float(gamma), None if alpha is None else tuple(alpha), bool(mean))
+
+
+class _PairFn(torch.autograd.Function):
+    """dice_loss / dice_loss1 / symmetric_mse_loss (utils/losses.py:8-27,107-116) through ustrun_pair_sums/_bwd."""
+
+    @staticmethod
+    def forward(ctx, a, b, kind):
+        a, b = _f32c(a, "input"), _f32c(b if b.dtype == torch.float32 else b.float(), "target")
+        if a.shape != b.shape:
+            raise RuntimeError(f"the two operands must have one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+        out = torch.empty(L.PAIR_NOUT, dtype=torch.float32, device=a.device)
+        part, nb = _partials(a.device)
+        L.check(L.lib().ustrun_pair_sums(a.data_ptr(), b.data_ptr(), a.numel(), out.data_ptr(), part.data_ptr(), nb, stream_ptr()), "ustrun_pair_sums")
+        ctx.save_for_backward(a, b, out)
+        ctx.kind = kind
+        return out[6 + _PAIR[kind]]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        a, b, out = ctx.saved_tensors
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        g = _upstream(g).reshape(1)
+        L.check(L.lib().ustrun_pair_sums_bwd(a.data_ptr(), b.data_ptr(), a.numel(), _PAIR[ctx.kind], out.data_ptr(), g.data_ptr(), L.ptr(da),
+                                             L.ptr(db), stream_ptr()), "ustrun_pair_sums_bwd")
+        return da, db, None
+
+
+def pair_loss(a, b, kind):
+    """One scalar over two tensors of one shape: "dice_sq" (squared sums below the line), "dice" (plain sums), "mse"."""
+    return _PairFn.apply(a, b, kind)
+
+
+class _RowKLFn(torch.autograd.Function):
+    """compute_kl_loss (utils/losses.py:284-295): softmax over the last dimension."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        a, b = _f32c(a, "p"), _f32c(b, "q")
+        if a.shape != b.shape or a.dim() < 1:
+            raise RuntimeError(f"the two operands must have one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+        C_ = a.shape[-1]
+        rows = a.numel() // C_
+        out = torch.empty(1, dtype=torch.float32, device=a.device)
+        part, nb = _partials(a.device)
+        L.check(L.lib().ustrun_row_kl_fwd(a.data_ptr(), b.data_ptr(), rows, C_, out.data_ptr(), part.data_ptr(), nb, stream_ptr()), "ustrun_row_kl_fwd")
+        ctx.save_for_backward(a, b)
+        ctx.cfg = (rows, C_)
+        return out[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        rows, C_ = ctx.cfg
+        a, b = ctx.saved_tensors
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        g = _upstream(g).reshape(1)
+        L.check(L.lib().ustrun_row_kl_bwd(a.data_ptr(), b.data_ptr(), rows, C_, g.data_ptr(), L.ptr(da), L.ptr(db), stream_ptr()), "ustrun_row_kl_bwd")
+        return da, db
+
+
+def row_kl(a, b):
+    return _RowKLFn.apply(a, b)
+
+
+class _ClassDiceFn(torch.autograd.Function):
+    """DiceLoss.forward (utils/losses.py:179-192): the per-class Dice of ustrun_dice_* with the smoothing term as an argument."""
+
+    @staticmethod
+    def forward(ctx, logits, target, act, weight, smooth):
+        import ctypes as C
+        logits = _f32c(logits, "inputs")
+        N, K, HW = _nkhw(logits, "inputs")
+        target = target.contiguous() if target.dtype == torch.int64 else _f32c(target.float(), "target")
+        w = None if weight is None else (C.c_float * K)(*[float(v) for v in weight])
+        out = torch.empty(1 + 3 * K, dtype=torch.float32, device=logits.device)
+        part, nb = _partials(logits.device)
+        cfg = (int(target.dtype == torch.int64), N, K, HW, _ACT[act], w, smooth)
+        L.check(L.lib().ustrun_dice_smooth_fwd(logits.data_ptr(), target.data_ptr(), cfg[0], 1, None, 0, N, K, HW, cfg[4], 0, w, smooth,
+                                               out.data_ptr(), part.data_ptr(), nb, stream_ptr()), "ustrun_dice_smooth_fwd")
+        ctx.save_for_backward(logits, target, out)
+        ctx.cfg = cfg
+        return out[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        logits, target, out = ctx.saved_tensors
+        t64, N, K, HW, act, w, smooth = ctx.cfg
+        dl, g = torch.empty_like(logits), _upstream(g).reshape(1)
+        L.check(L.lib().ustrun_dice_smooth_bwd(logits.data_ptr(), target.data_ptr(), t64, 1, None, 0, N, K, HW, act, 0, w, smooth,
+                                               out.data_ptr(), g.data_ptr(), 1.0, dl.data_ptr(), stream_ptr()), "ustrun_dice_smooth_bwd")
+        return dl, None, None, None, None
+
+
+def class_dice(logits, target, act="none", weight=None, smooth=1e-5):
+    """mean_k weight[k] (1 - (2 I_k + smooth) / (Z_k + Y_k + smooth)) on the one-hot of a class-index target with N*H*W elements."""
+    return _ClassDiceFn.apply(logits, target, act, weight, float(smooth))
+
+
 def pseudo_label(logits, threshold, mode):
     """train.py:648-667.  softmax -> (label int64 [N,H,W], mask f32 [N,1,H,W]); sigmoid -> f32 [N,K,H,W] x2."""
     lib = L.lib()
