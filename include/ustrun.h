@@ -97,6 +97,11 @@ int ustrun_bn_finalize(float* stat /* scratch: may be overwritten */, int mtiles
 int ustrun_bn_eval_affine(int C, const float* gamma, const float* beta, const float* running_mean,
                           const float* running_var, float eps, float* scale, float* shift,
                           ustrun_stream_t s);
+/* eval mode with the constants the backward through frozen statistics reads: aff[4][C] = {scale, shift, running_mean, rstd},
+ * rstd = 1 / sqrt(running_var + eps), scale / shift bit-identical to ustrun_bn_eval_affine (nn.BatchNorm2d in eval mode,
+ * unet_parts.py:17,20 under model.eval())                                                                              */
+int ustrun_bn_eval_consts(int C, const float* gamma, const float* beta, const float* running_mean,
+                          const float* running_var, float eps, float* aff, ustrun_stream_t s);
 /* materialise a = relu(y*scale+shift) as NHWC or NCHW f32 (block-level API and feature=True) */
 int ustrun_bn_relu_apply(const void* y, const float* scale, const float* shift, int64_t npix, int C,
                          int HW, float* out, int out_nchw, int dtype, ustrun_stream_t s);
@@ -167,6 +172,28 @@ int ustrun_bn_bwd_apply(const void* da, const void* dp, const void* y, const flo
 int ustrun_bn_bwd_apply_head(const float* dlogits, const float* head_w, const void* y, const float* scale, const float* shift,
                              const float* coef, int N, int H, int W, int C, int K, void* dy, int dtype, int passes,
                              int64_t aff_stride, ustrun_stream_t s);
+
+/* ---- BatchNorm+ReLU (+MaxPool) backward through FROZEN statistics: autograd of unet_parts.py:17-18,34 under model.eval(),
+ * where nn.BatchNorm2d normalises with its running buffers (networks/unet_model.py:25-39 is an ordinary autograd module in eval
+ * mode too).  With scale = gamma rstd, rstd = 1 / sqrt(running_var + eps), shift = beta - running_mean scale:
+ *   g = (da [+ dp routed to the window's first arg-max]) [y scale + shift > 0],  dy = scale g,
+ *   dbeta = sum g,  dgamma = rstd sum g (y - running_mean)   (mean = running_mean).
+ * dy does not depend on the sums, so ONE pass reads da, dp and y once each, writes dy (dy == da, in place, is allowed) and
+ * leaves per-block rows {sum g, sum g y} in `partials` (ustrun_bn_bwd_partials_bytes); a finalize adds the rows in a fixed order
+ * in f64.  No atomics: a repeated call is bit-identical.  accumulate != 0 adds to dgamma / dbeta.  dgamma == dbeta == NULL
+ * (frozen parameters): a pure apply pass -- no rows, no finalize, mean / rstd / partials unused and untouched.  No running
+ * buffer and no num_batches_tracked is written.  da may be NULL when dp is given; dp != NULL selects the 2x2 pooled windows
+ * (odd H / W included).  C a multiple of 4; USTRUN_F32X3 stores f32.                                                      */
+int ustrun_bn_bwd_frozen(const void* da, const void* dp, const void* y, const float* scale, const float* shift,
+                         const float* mean, const float* rstd, int N, int H, int W, int C, void* dy, float* dgamma,
+                         float* dbeta, int accumulate, float* partials, int64_t partials_bytes, int dtype, ustrun_stream_t s);
+/* the per-pass form: da / y / dy hold `passes` passes of N images each (dp: of N pooled images), pass g takes its constants at
+ * scale / shift / mean / rstd + g * aff_stride floats; dgamma / dbeta receive the passes' contributions one after the other, as
+ * `passes` calls of ustrun_bn_bwd_frozen with accumulate would add them                                                   */
+int ustrun_bn_bwd_frozen_passes(const void* da, const void* dp, const void* y, const float* scale, const float* shift,
+                                const float* mean, const float* rstd, int N, int H, int W, int C, void* dy, float* dgamma,
+                                float* dbeta, int accumulate, float* partials, int64_t partials_bytes, int dtype, int passes,
+                                int64_t aff_stride, ustrun_stream_t s);
 
 /* ---- conv3x3 input gradient (autograd of unet_parts.py:16,19) ------------------------------
  * da = conv3x3(dy, flipped/transposed w).  Channels [0,C0) go to da0[N,H,W,C0]; channels
@@ -510,6 +537,12 @@ int ustrun_unet_backward_part(const ustrun_unet_desc_t* d, const float* x, const
  *     first convolution (unet_parts.py:16); written by the part that reaches layer 0 (0, 2 or 4).  Rows of leading
  *     passes and of the tail pass are zero.  Needs C <= 4 and base a multiple of 8 up to 64.
  * With dfeat == dx == NULL this IS ustrun_unet_backward_part, launch for launch.                                          */
+/* d->train == 0: the backward through frozen BatchNorm (the forward must have run with the same eval descriptor; UNet under
+ * model.eval(), unet_model.py:25-39 with nn.BatchNorm2d on its running buffers): every layer's BatchNorm backward is the one-pass
+ * ustrun_bn_bwd_frozen, no running buffer moves; parts, dfeat, dx, groups / lead / tail and bilinear work as in train mode.
+ * grads == NULL (either mode): the input gradient alone -- needs dx, or a part that ends before layer 0 (1 or 3); no weight
+ * gradient, no head parameter gradient and no dgamma / dbeta is launched (eval mode: no sum and no finalize either; train mode
+ * keeps the sums its coefficients need).  dx is bit-identical to the call with gradients.                                  */
 int ustrun_unet_backward_io(const ustrun_unet_desc_t* d, const float* x, const float* dlogits, const float* dfeat,
                             void* workspace, void* scratch, float* const* grads, int accumulate, int part, float* dx,
                             ustrun_stream_t s);
@@ -627,8 +660,8 @@ int ustrun_debug_last_conv_variant(void);
  * ustrun_debug_last_conv_variant of the ConvTranspose / 1x1 GEMM kernel: 0x43540000 | (weights through registers ? 0x1000 : 0) |
  * (BN / 32) << 8 | (BK / 32) << 4 | mode (0 forward, 1 input gradient, 2 plain 1x1)                              */
 int ustrun_debug_last_wgrad_variant(void);
-/* the last BatchNorm-backward launch (ustrun_bn_bwd_reduce / _apply and the whole-network backward):
- * 0x424E0000 | pass << 8 (0 reduce, 1 apply) | element bytes << 4 | even-sized pooled windows << 2 | pooled << 1 |
+/* the last BatchNorm-backward launch (ustrun_bn_bwd_reduce / _apply / _frozen and the whole-network backward):
+ * 0x424E0000 | pass << 8 (0 reduce, 1 apply, 2 frozen) | element bytes << 4 | even-sized pooled windows << 2 | pooled << 1 |
  * eight channels (16 bytes) per lane; 0 before any                                                              */
 int ustrun_debug_last_bn_variant(void);
 /* the routes the calling thread's last ustrun_unet_backward / _part / _io call took at the two full-resolution layers:

@@ -257,16 +257,18 @@ __global__ void bn_eval_affine_kernel(int C, const float* gamma, const float* be
 // eval mode: the 18 layers' constants in ONE launch (blockIdx.y = layer x pass), instead of 18 five-microsecond ones
 struct EvalAffineJobs {
     const float *gamma[18], *beta[18], *rm[18], *rv[18];
-    float* aff[18];          // layer's table: pass g at aff + g * 4C: {scale[C], shift[C], ...}
+    float* aff[18];          // layer's table: pass g at aff + g * 4C: {scale[C], shift[C], running_mean[C], rstd[C]}
     int C[18];
 };
 __global__ void bn_eval_affine_multi_kernel(const EvalAffineJobs j, float eps, int passes) {
     const int l = blockIdx.y / passes, g = blockIdx.y % passes, C = j.C[l];
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c < C) {
-        const float sc = j.gamma[l][c] * (1.0f / sqrtf(j.rv[l][c] + eps));
+        const float rs = 1.0f / sqrtf(j.rv[l][c] + eps);
+        const float sc = j.gamma[l][c] * rs;
         float* a = j.aff[l] + 4L * C * g;
         a[c] = sc; a[C + c] = j.beta[l][c] - j.rm[l][c] * sc;
+        a[2 * C + c] = j.rm[l][c]; a[3 * C + c] = rs;       // mean, rstd: what the frozen backward's dgamma needs
     }
 }
 
@@ -861,6 +863,174 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_x8_kernel(const elt_t* __re
     }
 }
 
+// ---- frozen BatchNorm (running statistics): the backward in ONE pass ----------------------------------------------------------
+// With scale = gamma rstd and shift = beta - running_mean scale fixed, dy = scale g with g = (da [+ routed dp]) [y scale + shift > 0]
+// needs no batch sum: the apply pass does not wait for a reduce pass, and both read the same da, dp and y -- so one kernel reads
+// each once, writes dy (in place where dy == da: a thread owns its window's elements, loaded before they are stored) and, SUMS,
+// leaves the block's row {sum g, sum g y} for bn_bwd_frozen_finalize_kernel.  SUMS = false (frozen parameters): a pure apply pass,
+// no LDS, no row.  Thread = (channel quad, window lane) as in bn_bwd_reduce_kernel; one window per trip as in bn_bwd_apply_kernel
+// (loads and stores of several windows queue behind each other there).
+template <bool POOL, int ESZ, bool EVEN, bool SUMS>
+__global__ __launch_bounds__(256) void bn_bwd_frozen_kernel(const float* da, const float* __restrict__ dp, const float* __restrict__ y,
+                                                           const float* __restrict__ scale, const float* __restrict__ shift,
+                                                           int N, int H, int W, int C, int G, float* dy,
+                                                           float* __restrict__ partials, const PassOff po) {
+    constexpr int NPX = Win<POOL>::NPX;
+    {
+        const long g = blockIdx.y;
+        if (da) da = (const float*)((const char*)da + g * po.act * ESZ);
+        if (dp) dp = (const float*)((const char*)dp + g * po.pool * ESZ);
+        y = (const float*)((const char*)y + g * po.act * ESZ);
+        dy = (float*)((char*)dy + g * po.act * ESZ);
+        scale += g * po.aff; shift += g * po.aff;
+        if (SUMS) partials += g * po.part;
+    }
+    __shared__ f32x4 red[SUMS ? 2 : 1][SUMS ? 256 : 1];
+    const int C4 = C / 4, PL = 256 / G;
+    const int cq0 = threadIdx.x % G, pl = threadIdx.x / G;
+    const int WH = POOL ? (H + 1) / 2 : H, WW = POOL ? (W + 1) / 2 : W;
+    const long nwin = (long)N * WH * WW;
+    const long stride = (long)gridDim.x * PL;
+    for (int cb = 0; cb < C4; cb += G) {      // uniform trip count: with SUMS the body holds barriers
+        const int cq = cb + cq0;
+        const bool active = cq < C4;
+        const int c = active ? cq * 4 : 0;
+        const f32x4 sc = *(const f32x4*)(scale + c), sh = *(const f32x4*)(shift + c);
+        f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+        if (active) {
+            for (long w = (long)blockIdx.x * PL + pl; w < nwin; w += stride) {
+                f32x4 yv[NPX], dz[NPX]; bool ok[NPX];
+                window_dz<POOL, ESZ, EVEN>(da, dp, y, sc, sh, w, WH, WW, H, W, C, c, yv, dz, ok);
+                long base = w * C + c;                       // plain: the pixel itself
+                if (POOL) {
+                    const unsigned uw = (unsigned)w, per = (unsigned)(WH * WW);
+                    const unsigned n = uw / per, rem = uw - n * per, wy = rem / (unsigned)WW, wx = rem - wy * (unsigned)WW;
+                    base = (((long)n * H + 2 * wy) * W + 2 * wx) * C + c;
+                }
+#pragma unroll
+                for (int q = 0; q < NPX; ++q) {
+                    if (SUMS) { s1 += dz[q]; s2 += dz[q] * yv[q]; }       // (pixels outside the map carry dz = y = 0)
+                    if (!ok[q]) continue;
+                    st4t<ESZ>(dy, base + ((long)(q >> 1) * W + (q & 1)) * C, sc * dz[q]);
+                }
+            }
+        }
+        if constexpr (SUMS) {
+            red[0][threadIdx.x] = s1; red[1][threadIdx.x] = s2;
+            __syncthreads();
+            if (pl == 0 && active) {                         // fixed order over the block's window lanes
+                for (int k = 1; k < PL; ++k) { s1 += red[0][k * G + cq0]; s2 += red[1][k * G + cq0]; }
+                *(f32x4*)(partials + ((long)blockIdx.x * 2 + 0) * C + c) = s1;
+                *(f32x4*)(partials + ((long)blockIdx.x * 2 + 1) * C + c) = s2;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// The plain 16-bit form with 8 channels = 16 bytes per lane, two pixels in flight per trip (bn_bwd_apply_x8_kernel's shape; the
+// sums in ascending pixel order as bn_bwd_reduce_x8_kernel forms them)
+template <bool SUMS>
+__global__ __launch_bounds__(256) void bn_bwd_frozen_x8_kernel(const elt_t* da, const elt_t* __restrict__ y,
+                                                              const float* __restrict__ scale, const float* __restrict__ shift,
+                                                              long npix, int C, int G8, elt_t* dy, float* __restrict__ partials,
+                                                              const PassOff po) {
+    {
+        const long g = blockIdx.y;
+        da += g * po.act; y += g * po.act; dy += g * po.act;
+        scale += g * po.aff; shift += g * po.aff;
+        if (SUMS) partials += g * po.part;
+    }
+    __shared__ f32x4 red[SUMS ? 4 : 1][SUMS ? 256 : 1];
+    const int PL = 256 / G8;
+    const int g8 = threadIdx.x % G8, c = 8 * g8, pl = threadIdx.x / G8;
+    const F8 sc = ld8f(scale + c), sh = ld8f(shift + c);
+    F8 s1 = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, s2 = s1;
+    const long stride = (long)gridDim.x * PL;
+    constexpr int U = 2;
+    long w = (long)blockIdx.x * PL + pl;
+    auto one = [&](bf16x8 yb, bf16x8 db) {
+        const F8 yv = up8(yb), dv = up8(db);
+        bf16x8 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float al = yv.lo[j] * sc.lo[j] + sh.lo[j], ah = yv.hi[j] * sc.hi[j] + sh.hi[j];
+            const float zl = al > 0.f ? dv.lo[j] : 0.f, zh = ah > 0.f ? dv.hi[j] : 0.f;
+            if (SUMS) {
+                s1.lo[j] += zl; s1.hi[j] += zh;
+                s2.lo[j] += zl * yv.lo[j]; s2.hi[j] += zh * yv.hi[j];
+            }
+            o[j] = (elt_t)(sc.lo[j] * zl); o[4 + j] = (elt_t)(sc.hi[j] * zh);
+        }
+        return o;
+    };
+    for (; w + (U - 1) * stride < npix; w += U * stride) {
+        bf16x8 yb[U], db[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { yb[u] = *(const bf16x8*)(y + (w + u * stride) * C + c); db[u] = *(const bf16x8*)(da + (w + u * stride) * C + c); }
+#pragma unroll
+        for (int u = 0; u < U; ++u) *(bf16x8*)(dy + (w + u * stride) * C + c) = one(yb[u], db[u]);
+    }
+    for (; w < npix; w += stride)
+        *(bf16x8*)(dy + w * C + c) = one(*(const bf16x8*)(y + w * C + c), *(const bf16x8*)(da + w * C + c));
+    if constexpr (SUMS) {
+        red[0][threadIdx.x] = s1.lo; red[1][threadIdx.x] = s1.hi; red[2][threadIdx.x] = s2.lo; red[3][threadIdx.x] = s2.hi;
+        __syncthreads();
+        if (pl == 0) {                                              // fixed order over the block's pixel lanes
+            for (int k = 1; k < PL; ++k) {
+                s1.lo += red[0][k * G8 + g8]; s1.hi += red[1][k * G8 + g8];
+                s2.lo += red[2][k * G8 + g8]; s2.hi += red[3][k * G8 + g8];
+            }
+            float* r0 = partials + ((long)blockIdx.x * 2 + 0) * C + c;
+            float* r1 = partials + ((long)blockIdx.x * 2 + 1) * C + c;
+            *(f32x4*)r0 = s1.lo; *(f32x4*)(r0 + 4) = s1.hi;
+            *(f32x4*)r1 = s2.lo; *(f32x4*)(r1 + 4) = s2.hi;
+        }
+    }
+}
+
+// partials[pass][rows][2][C] -> dbeta = sum g, dgamma = rstd (sum g y - running_mean sum g): the rows of a pass added in f64 on
+// eight row lanes in bn_bwd_finalize_kernel's order, the passes' contributions one after the other as separate calls would add
+// them.  No coefficient table: dy does not depend on the sums.
+__global__ void bn_bwd_frozen_finalize_kernel(const float* __restrict__ partials, int rows, int C, const float* __restrict__ mean,
+                                              const float* __restrict__ rstd, float* dgamma, float* dbeta, int accumulate,
+                                              int passes, const PassOff po) {
+    __shared__ double red[2][32][32];
+    const int cl = threadIdx.x & 31, rg = threadIdx.x >> 5;      // 32 channels x 32 row lanes
+    const int c = blockIdx.x * 32 + cl;
+    float dg_run = 0.f, db_run = 0.f;
+    if (rg == 0 && c < C && accumulate) { dg_run = dgamma[c]; db_run = dbeta[c]; }
+    constexpr int LPP = 8, PPR = 32 / LPP;
+    const int gl = rg / LPP, lane = rg % LPP;
+    for (int g0 = 0; g0 < passes; g0 += PPR) {
+        const int g = g0 + gl;
+        double s1 = 0.0, s2 = 0.0;
+        if (c < C && g < passes) {
+            const float* pt = partials + (long)g * po.part + c;
+#pragma unroll 8
+            for (int r = lane; r < rows; r += LPP) {
+                s1 += (double)pt[(long)r * 2 * C];
+                s2 += (double)pt[(long)r * 2 * C + C];
+            }
+        }
+        red[0][rg][cl] = s1; red[1][rg][cl] = s2;
+        __syncthreads();
+        if (rg == 0 && c < C) {
+            for (int q = 0; q < PPR && g0 + q < passes; ++q) {
+                double t1 = 0.0, t2 = 0.0;
+                for (int k = 0; k < LPP; ++k) { t1 += red[0][q * LPP + k][cl]; t2 += red[1][q * LPP + k][cl]; }
+                const int gq = g0 + q;
+                const double mu = mean[(long)gq * po.aff + c], rs = rstd[(long)gq * po.aff + c];
+                const double dbe = t1, dga = rs * (t2 - mu * t1);
+                if (gq == 0 && !accumulate) { dg_run = (float)dga; db_run = (float)dbe; }
+                else { dg_run = dg_run + (float)dga; db_run = db_run + (float)dbe; }
+            }
+        }
+        __syncthreads();
+    }
+    if (rg == 0 && c < C) { dgamma[c] = dg_run; dbeta[c] = db_run; }
+}
+
 // 8-channel kernels: bf16, no pooling, C / 8 a power of two <= 256 (every layer of the U-Net and of ResNet-50/101);
 // ustrun_debug_flags bit 12 (4096) keeps the 4-channel kernels (A/B runs)
 static bool x8_ok(int C, bool pool, int dtype) {
@@ -869,7 +1039,7 @@ static bool x8_ok(int C, bool pool, int dtype) {
     return dtype == USTRUN_D16 && !pool && C % 8 == 0 && g8 >= 1 && g8 <= 256 && (g8 & (g8 - 1)) == 0;
 }
 
-// ustrun_debug_last_bn_variant: 0x424E0000 ('BN') | pass (0 reduce, 1 apply) << 8 | element bytes << 4 | even windows << 2 |
+// ustrun_debug_last_bn_variant: 0x424E0000 ('BN') | pass (0 reduce, 1 apply, 2 frozen) << 8 | element bytes << 4 | even windows << 2 |
 // pooled << 1 | eight channels per lane; per calling thread
 thread_local int g_last_bn_variant = 0;
 void note_bn_variant(int pass, int esz, bool even, bool pool, bool x8) {
@@ -1224,6 +1394,94 @@ extern "C" int ustrun_bn_bwd_apply(const void* da, const void* dp, const void* y
                                    const float* shift, const float* coef, int N, int H, int W, int C, void* dy,
                                    int dtype, ustrun_stream_t s) {
     return bn_bwd_apply_passes(da, dp, y, scale, shift, coef, N, H, W, C, dy, dtype, 1, 0, 0, 0, (hipStream_t)s);
+}
+
+namespace ustrun {
+// Frozen BatchNorm's backward, one launch for all passes (+ the finalize when the parameters want gradients): see
+// bn_bwd_frozen_kernel.  dgamma == nullptr: no rows, no finalize, `partials` untouched.
+int bn_bwd_frozen_passes(const void* da, const void* dp, const void* y, const float* scale, const float* shift, const float* mean,
+                         const float* rstd, int N, int H, int W, int C, void* dy, float* dgamma, float* dbeta, int accumulate,
+                         float* partials, int64_t partials_bytes, int dtype, int passes, long act_elems, long pool_elems,
+                         long aff_stride, hipStream_t s) {
+    USTRUN_CHECK(dtype_ok(dtype), "bn_bwd_frozen: dtype %d not built", dtype);
+    USTRUN_CHECK((da || dp) && y && scale && shift && dy, "bn_bwd_frozen: null pointer");
+    USTRUN_CHECK(N > 0 && H > 0 && W > 0 && C % 4 == 0 && C > 0 && passes >= 1 && passes <= 64,
+                 "bn_bwd_frozen: N=%d H=%d W=%d C=%d (a multiple of 4) passes=%d", N, H, W, C, passes);
+    const bool sums = dgamma != nullptr;
+    USTRUN_CHECK(sums == (dbeta != nullptr), "bn_bwd_frozen: dgamma and dbeta come together");
+    USTRUN_CHECK(!sums || (mean && rstd && partials), "bn_bwd_frozen: the sums need mean, rstd and the partials scratch");
+    USTRUN_CHECK(!sums || partials_bytes >= ustrun_bn_bwd_partials_bytes((int64_t)N * H * W, C), "bn_bwd_frozen: partials too small");
+    const bool pool = dp != nullptr;
+    USTRUN_CHECK(!pool || (H >= 2 && W >= 2), "bn_bwd_frozen: pooled windows need H, W >= 2 (%dx%d)", H, W);
+    const bool x8 = x8_ok(C, pool, dtype) && da;
+    const int G = x8 ? C / 8 : group_size(C / 4);
+    const long nwin = pool ? (long)N * ((H + 1) / 2) * ((W + 1) / 2) : (long)N * H * W;
+    USTRUN_CHECK(nwin < (1L << 31), "bn_bwd_frozen: %ld windows per pass", nwin);
+    const int PL = 256 / G;
+    long blocks;
+    if (sums) {             // the passes' rows share the 1024-row table, as bn_bwd_reduce's do
+        blocks = reduce_blocks(nwin, G);
+        if (blocks > 1024 / passes) blocks = 1024 / passes;
+    } else {                // a pure apply pass: bn_bwd_apply's grid
+        blocks = (nwin + (long)PL * 4 - 1) / ((long)PL * 4);
+        if (blocks > 4096) blocks = 4096;
+    }
+    const PassOff po = {act_elems, pool_elems, aff_stride, blocks * 2 * C, 0};
+    const bool even = pool && !(H & 1) && !(W & 1);
+    note_bn_variant(2, act_esz(dtype), even, pool, x8);
+    const dim3 grid((int)blocks, passes);
+    if (x8) {
+        if (sums) hipLaunchKernelGGL(bn_bwd_frozen_x8_kernel<true>, grid, dim3(256), 0, s, (const elt_t*)da, (const elt_t*)y, scale,
+                                     shift, nwin, C, G, (elt_t*)dy, partials, po);
+        else hipLaunchKernelGGL(bn_bwd_frozen_x8_kernel<false>, grid, dim3(256), 0, s, (const elt_t*)da, (const elt_t*)y, scale, shift,
+                                nwin, C, G, (elt_t*)dy, partials, po);
+    } else {
+#define USTRUN_BN_FROZEN(P, E, V)                                                                                                   \
+    do {                                                                                                                            \
+        if (sums) hipLaunchKernelGGL((bn_bwd_frozen_kernel<P, E, V, true>), grid, dim3(256), 0, s, (const float*)da, (const float*)dp, \
+                                     (const float*)y, scale, shift, N, H, W, C, G, (float*)dy, partials, po);                       \
+        else hipLaunchKernelGGL((bn_bwd_frozen_kernel<P, E, V, false>), grid, dim3(256), 0, s, (const float*)da, (const float*)dp,  \
+                                (const float*)y, scale, shift, N, H, W, C, G, (float*)dy, partials, po);                            \
+    } while (0)
+        if (dtype == USTRUN_D16) { if (even) USTRUN_BN_FROZEN(true, 2, true); else if (pool) USTRUN_BN_FROZEN(true, 2, false); else USTRUN_BN_FROZEN(false, 2, false); }
+        else { if (even) USTRUN_BN_FROZEN(true, 4, true); else if (pool) USTRUN_BN_FROZEN(true, 4, false); else USTRUN_BN_FROZEN(false, 4, false); }
+#undef USTRUN_BN_FROZEN
+    }
+    USTRUN_LAUNCH_CHECK("bn_bwd_frozen");
+    if (sums) {
+        hipLaunchKernelGGL(bn_bwd_frozen_finalize_kernel, dim3(cdiv(C, 32)), dim3(1024), 0, s, partials, (int)blocks, C, mean, rstd,
+                           dgamma, dbeta, accumulate, passes, po);
+        USTRUN_LAUNCH_CHECK("bn_bwd_frozen_finalize");
+    }
+    return 0;
+}
+}  // namespace ustrun
+
+extern "C" int ustrun_bn_bwd_frozen(const void* da, const void* dp, const void* y, const float* scale, const float* shift,
+                                    const float* mean, const float* rstd, int N, int H, int W, int C, void* dy, float* dgamma,
+                                    float* dbeta, int accumulate, float* partials, int64_t partials_bytes, int dtype,
+                                    ustrun_stream_t s) {
+    return bn_bwd_frozen_passes(da, dp, y, scale, shift, mean, rstd, N, H, W, C, dy, dgamma, dbeta, accumulate, partials,
+                                partials_bytes, dtype, 1, 0, 0, 0, (hipStream_t)s);
+}
+
+extern "C" int ustrun_bn_bwd_frozen_passes(const void* da, const void* dp, const void* y, const float* scale, const float* shift,
+                                           const float* mean, const float* rstd, int N, int H, int W, int C, void* dy,
+                                           float* dgamma, float* dbeta, int accumulate, float* partials, int64_t partials_bytes,
+                                           int dtype, int passes, int64_t aff_stride, ustrun_stream_t s) {
+    return bn_bwd_frozen_passes(da, dp, y, scale, shift, mean, rstd, N, H, W, C, dy, dgamma, dbeta, accumulate, partials,
+                                partials_bytes, dtype, passes, (long)N * H * W * C, (long)N * (H / 2) * (W / 2) * C, (long)aff_stride,
+                                (hipStream_t)s);
+}
+
+extern "C" int ustrun_bn_eval_consts(int C, const float* gamma, const float* beta, const float* running_mean,
+                                     const float* running_var, float eps, float* aff, ustrun_stream_t s) {
+    USTRUN_CHECK(C > 0 && aff, "bn_eval_consts: bad args");
+    const int c1[1] = {C};
+    const float* const g1[1] = {gamma}; const float* const b1[1] = {beta};
+    const float* const m1[1] = {running_mean}; const float* const v1[1] = {running_var};
+    float* const a1[1] = {aff};
+    return bn_eval_affine_layers(1, c1, g1, b1, m1, v1, a1, eps, 1, (hipStream_t)s);
 }
 
 extern "C" int ustrun_debug_last_bn_variant(void) { return g_last_bn_variant; }

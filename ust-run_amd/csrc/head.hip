@@ -412,7 +412,8 @@ int head_bwd_passes(const float* dlogits, const void* y, const float* scale, con
                     int K, const float* w, void* da, float* dw, float* db, int accumulate, float* partials,
                     int64_t partials_bytes, int dtype, int passes, long pass_aff, hipStream_t s, int* bn_rows) {
     USTRUN_CHECK(dtype_ok(dtype), "head_bwd: dtype %d not built", dtype);
-    USTRUN_CHECK(dlogits && y && w && dw && db && partials, "head_bwd: null pointer");        // (da null: the gradient is not stored)
+    USTRUN_CHECK(dlogits && y && w && partials, "head_bwd: null pointer");        // (da null: the gradient is not stored)
+    USTRUN_CHECK((dw != nullptr) == (db != nullptr), "head_bwd: dw and db come together");    // (both null: the input gradient alone)
     USTRUN_CHECK(C % 4 == 0 && C > 0 && K >= 1 && K <= KMAX, "head_bwd: C=%d K=%d unsupported", C, K);
     USTRUN_CHECK(npix > 0 && HW > 0 && npix < (1LL << 32) && passes >= 1, "head_bwd: bad extent");
     const int LPP = lanes_per_pixel(C / 4);
@@ -435,6 +436,7 @@ int head_bwd_passes(const float* dlogits, const void* y, const float* scale, con
     else { if (K == 2) USTRUN_HB(4, 2); else if (K == 4) USTRUN_HB(4, 4); else USTRUN_HB(4, 0); }
 #undef USTRUN_HB
     USTRUN_LAUNCH_CHECK("head_bwd");
+    if (!dw) return 0;
     USTRUN_TRY(reduce_rows(partials, blocks * passes, row, 0, K * C, dw, accumulate, s));
     USTRUN_TRY(reduce_rows(partials, blocks * passes, row, (long)K * C, K, db, accumulate, s));
     return 0;
@@ -444,7 +446,7 @@ int head_bwd_passes(const float* dlogits, const void* y, const float* scale, con
 extern "C" int ustrun_head_bwd(const float* dlogits, const void* y, const float* scale, const float* shift,
                                int64_t npix, int HW, int C, int K, const float* w, void* da, float* dw, float* db,
                                int accumulate, float* partials, int64_t partials_bytes, int dtype, ustrun_stream_t s) {
-    USTRUN_CHECK(da, "head_bwd: null pointer");
+    USTRUN_CHECK(da && dw && db, "head_bwd: null pointer");
     return head_bwd_passes(dlogits, y, scale, shift, npix, HW, C, K, w, da, dw, db, accumulate, partials, partials_bytes, dtype, 1,
                            0, (hipStream_t)s, nullptr);
 }

@@ -423,8 +423,14 @@ extern "C" int ustrun_unet_backward_io(const ustrun_unet_desc_t* d, const float*
     USTRUN_CHECK(which >= 0 && which <= 4, "unet_backward: part %d", which);
     Plan p; USTRUN_TRY(make_plan(d, p));
     ShortLastPass declared_tail(p.T > 0);
-    USTRUN_CHECK(x && (dlogits || dfeat || which > 1) && workspace && scratch && grads && d->packed, "unet_backward: null pointer");
-    USTRUN_CHECK(d->train, "unet_backward: forward must have run in train mode");
+    USTRUN_CHECK(x && (dlogits || dfeat || which > 1) && workspace && scratch && d->packed, "unet_backward: null pointer");
+    // grads == NULL: the input gradient alone (no weight, head-parameter, dgamma or dbeta launch) -- something must come out of it
+    USTRUN_CHECK(grads || dx || which == 1 || which == 3, "unet_backward: no parameter gradients and no dx: nothing to compute");
+    // d->train == 0: the forward ran on the running statistics (its tables hold scale, shift, running_mean, rstd): every layer's
+    // BatchNorm backward is the one-pass bn_bwd_frozen_passes -- dy does not wait for sums, so no coefficient table, no fused-sum
+    // epilogue and no apply-on-load route is taken
+    const bool frozen = !d->train, wg = grads != nullptr;
+    auto gp = [&](int k) -> float* { return wg ? grads[k] : nullptr; };
     USTRUN_CHECK(!dx || (p.C <= 4 && p.base % 8 == 0 && p.base <= 64),
                  "unet_backward: the input gradient is built for C <= 4 and base a multiple of 8 up to 64 (C=%d base=%d)", p.C, p.base);
     const char* ws = (const char*)workspace;
@@ -450,7 +456,7 @@ extern "C" int ustrun_unet_backward_io(const ustrun_unet_desc_t* d, const float*
         const long gpix = (long)p.gN * p.H * p.W;
         // With K classes da17 is K multiply-adds on 4 K bytes of dlogits per pixel: cheaper to form twice than to store (128 B per
         // pixel) and load once.  Its only other reader would be the reduce pass, so the head must have formed the sums itself.
-        const bool sums_in_head = !(g_debug_flags & 8388608) && !dfeat;
+        const bool sums_in_head = !(g_debug_flags & 8388608) && !dfeat && !frozen;
         // (not with the stop-early aid of bits 16-20, whose users read da17 from the scratch)
         da17_from_dl = !keep17 && dlogits && sums_in_head && dt == USTRUN_D16 && bn_bwd_apply_head_ok(C, p.K, dt) &&
                        gpix < (1L << 31) && !((g_debug_flags >> 16) & 31);
@@ -458,9 +464,9 @@ extern "C" int ustrun_unet_backward_io(const ustrun_unet_desc_t* d, const float*
         // BatchNorm backward runs its reduce pass over the summed da)
         if (dlogits)
         USTRUN_TRY(head_bwd_passes(dlogits, yb(17), affp(17), affp(17) + C, gpix, p.H * p.W, C, p.K, d->head_w,
-                                   da17_from_dl ? nullptr : sc + p.da_off[17], grads[p.gi_head], grads[p.gi_head + 1], accumulate, part,
+                                   da17_from_dl ? nullptr : sc + p.da_off[17], gp(p.gi_head), gp(p.gi_head + 1), accumulate, part,
                                    p.part_bytes, dt, p.Gb, 4L * C, (hipStream_t)s, sums_in_head ? &head_bn_rows : nullptr));
-        else if (!accumulate) {     // no gradient at the logits: the head's parameters get zeros
+        else if (!accumulate && wg) {     // no gradient at the logits: the head's parameters get zeros
             hipError_t e = hipMemsetAsync(grads[p.gi_head], 0, sizeof(float) * p.K * C, (hipStream_t)s);
             if (e == hipSuccess) e = hipMemsetAsync(grads[p.gi_head + 1], 0, sizeof(float) * p.K, (hipStream_t)s);
             USTRUN_CHECK(e == hipSuccess, "unet_backward: zeroing the head's gradients: %s", hipGetErrorString(e));
@@ -485,22 +491,26 @@ extern "C" int ustrun_unet_backward_io(const ustrun_unet_desc_t* d, const float*
         const int ns = conv_sources(p, x, ws, i, srcs, true);
         // Layer 0 without dx: dy0's only reader is the first convolution's weight gradient, which then forms it from da0 and y0 in its
         // loader (conv_first_wgrad_bn) -- no apply pass, no dy0 written and read back.  conv_first_dgrad needs the stored dy0.
-        const bool dy0_on_load = i == 0 && !keep0 && !dx && dt == USTRUN_D16 && ns == 1 &&
+        const bool dy0_on_load = i == 0 && !keep0 && !dx && !frozen && wg && dt == USTRUN_D16 && ns == 1 &&
                                  conv_first_wgrad_bn_ok(srcs[0], p.Nb, H, W, C, dt) && !((g_debug_flags >> 16) & 31);
         {   // BatchNorm backward is a per-pass reduction: all passes in one launch per kernel (blockIdx.y = pass)
             const long act = (long)p.gN * H * W * C, pl = (long)p.gN * (H / 2) * (W / 2) * C;
+            if (frozen) {                           // one pass, in place: dy over da, the rows of the sums only where gradients are wanted
+                USTRUN_TRY(bn_bwd_frozen_passes(da, dp, yb(i), aff, aff + C, aff + 2 * C, aff + 3 * C, p.gN, H, W, C, da, gp(gi + 1),
+                                                gp(gi + 2), accumulate, part, p.part_bytes, dt, p.Gb, act, pl, 4L * C, (hipStream_t)s));
+            } else {
             if (i == 17 && head_bn_rows > 0) {      // the sums came with the head's partial rows: no reduce pass over da and y
                 const long row = (long)p.K * C + p.K + 2L * C;
                 USTRUN_TRY(bn_bwd_finalize_rows(part, head_bn_rows, row, (long)p.K * C + p.K, C, (int64_t)p.gN * H * W, d->bn_w[i],
-                                                aff + 2 * C, aff + 3 * C, grads[gi + 1], grads[gi + 2], accumulate, coef, p.Gb,
+                                                aff + 2 * C, aff + 3 * C, gp(gi + 1), gp(gi + 2), accumulate, coef, p.Gb,
                                                 4L * C, (hipStream_t)s));
             } else if (dgrad_bn_rows > 0) {         // ... or with the rows the producing input gradient wrote (below)
                 USTRUN_CHECK(dgrad_bn_rows % p.Gb == 0, "unet_backward: %d sum rows do not split into %d passes", dgrad_bn_rows, p.Gb);
                 USTRUN_TRY(bn_bwd_finalize_stat(part, dgrad_bn_rows / p.Gb, p.Gb, C, (int64_t)p.gN * H * W, d->bn_w[i], aff + 2 * C,
-                                                aff + 3 * C, 4L * C, grads[gi + 1], grads[gi + 2], accumulate, coef, (hipStream_t)s));
+                                                aff + 3 * C, 4L * C, gp(gi + 1), gp(gi + 2), accumulate, coef, (hipStream_t)s));
             } else
             USTRUN_TRY(bn_bwd_reduce_passes(da, dp, yb(i), aff, aff + C, aff + 2 * C, aff + 3 * C, d->bn_w[i], p.gN, H, W,
-                                            C, grads[gi + 1], grads[gi + 2], accumulate, coef, part, p.part_bytes, dt, p.Gb, act,
+                                            C, gp(gi + 1), gp(gi + 2), accumulate, coef, part, p.part_bytes, dt, p.Gb, act,
                                             pl, 4L * C, (hipStream_t)s));
             if (i == 17 && da17_from_dl) {
                 USTRUN_CHECK(head_bn_rows > 0, "unet_backward: the head formed no BatchNorm-backward sums");
@@ -510,16 +520,18 @@ extern "C" int ustrun_unet_backward_io(const ustrun_unet_desc_t* d, const float*
             } else if (!dy0_on_load)
             USTRUN_TRY(bn_bwd_apply_passes(da, dp, yb(i), aff, aff + C, coef, p.gN, H, W, C, da, dt, p.Gb, act, pl,
                                            4L * C, (hipStream_t)s));
+            }
         }
         dgrad_bn_rows = 0;
-        prof_set_tag(200 + i, p.Nb);
-        if (dy0_on_load) {
+        if (dy0_on_load) {          // (never without grads: the input gradient alone launches no weight gradient)
+            prof_set_tag(200 + i, p.Nb);
             const int rc = conv_first_wgrad_bn(srcs[0], da, yb(0), aff, aff + C, coef, p.gN, 4L * C, p.Nb, grads[gi], accumulate, part,
                                                p.part_bytes, (hipStream_t)s);
             prof_set_tag(-1, 0);
             USTRUN_TRY(rc);
             g_last_backward_route |= 2;
-        } else {
+        } else if (wg) {
+        prof_set_tag(200 + i, p.Nb);
         USTRUN_TRY(ustrun_conv3x3_wgrad(srcs, ns, da, p.Nb, H, W, C, grads[gi], accumulate, part, p.part_bytes, dt, s));
         prof_set_tag(-1, 0);
         }
@@ -557,16 +569,18 @@ extern "C" int ustrun_unet_backward_io(const ustrun_unet_desc_t* d, const float*
             ustrun_src_t a = nhwc_src(yb(prev), affp(prev), p.cout[prev], p.Hs[l + 1], p.Ws[l + 1], 1, 0,
                                       p.pgb);
             const int ub = 30 + j * 8;
+            if (wg) {
             prof_set_tag(220 + j, p.Nb);
             USTRUN_TRY(ustrun_convT2x2_wgrad(&a, sc + p.du_off[j], p.Nb, p.Hs[l + 1], p.Ws[l + 1], p.up_cout[j], grads[ub],
                                              grads[ub + 1], accumulate, part, p.part_bytes, dt, s));
+            }
             prof_set_tag(120 + j, p.Nb);
             // (da of the conv2 one level down: its BatchNorm-backward sums ride along where the layer is handled by this same call)
             const float* pa = affp(prev);
             const int Cp = p.up_cin[j];
             // (not for down4's second BatchNorm, j = 0: the backward may be split right there -- parts 1 | 2 -- and the split and
             // the un-split call must sum in the same order: test_backward_in_two_parts_equals_one_call)
-            if (!(g_debug_flags & (1 << 25)) && j > 0 && prev >= i_lo &&
+            if (!frozen && !(g_debug_flags & (1 << 25)) && j > 0 && prev >= i_lo &&
                 (long)ustrun_conv_mtiles(p.Nb, p.Hs[l + 1], p.Ws[l + 1], Cp) * 2 * Cp * 4 <= p.part_bytes)
                 USTRUN_TRY(ustrun_convT2x2_dgrad_bnsum(sc + p.du_off[j], pk + p.ud_off[j], p.Nb, p.Hs[l + 1], p.Ws[l + 1], p.up_cout[j], Cp,
                                                        sc + p.da_off[prev], yb(prev), pa, pa + Cp, p.pgb, 4L * Cp,
@@ -581,7 +595,7 @@ extern "C" int ustrun_unet_backward_io(const ustrun_unet_desc_t* d, const float*
             const float* pa = affp(i - 1);
             const int Cp = p.cin[i];
             const long need = (long)ustrun_conv_mtiles(p.Nb, H, W, Cp) * 2 * Cp * 4;
-            if (!(g_debug_flags & (1 << 25)) && i - 1 >= i_lo && need <= p.part_bytes)
+            if (!frozen && !(g_debug_flags & (1 << 25)) && i - 1 >= i_lo && need <= p.part_bytes)
                 USTRUN_TRY(ustrun_conv3x3_dgrad_bnsum(da, wd, p.Nb, H, W, C, Cp, sc + p.da_off[i - 1], yb(i - 1), pa, pa + Cp,
                                                       p.pgb, 4L * Cp, part, &dgrad_bn_rows, dt, s));
             if (dgrad_bn_rows == 0)

@@ -18,6 +18,11 @@ class UNet(nn.Module):
         self.bilinear = bilinear
         self.base_channels = base_channels       # 64 in the reference; smaller only for cheap tests
         self.compute_dtype = dtype
+        # (additive) True: in eval mode the call records its autograd node too, and the backward goes through BatchNorm frozen on its
+        # running statistics (ustrun_unet_backward_io with train = 0).  Off by default: an eval-mode call then keeps what it always did
+        # -- no node, the forward's workspace freed on return even when the caller forgot torch.no_grad() -- and x.requires_grad in
+        # eval mode raises, naming this switch.  A plain attribute, not part of the state_dict.
+        self.eval_backward = False
         b = base_channels
 
         self.inc = DoubleConv(n_channels, b)

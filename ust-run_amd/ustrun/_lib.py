@@ -60,6 +60,7 @@ SIGNATURES = {
     "ustrun_conv3x3_fwd_rows": (i32, [PSrc, i32, vp, i32, i32, i32, i32, vp, fp, C.POINTER(C.c_int), i32, vp]),
     "ustrun_bn_finalize": (i32, [fp, i32, i32, i64, fp, fp, fp, fp, vp, f32, f32, i32, fp, fp, fp, fp, vp]),
     "ustrun_bn_eval_affine": (i32, [i32, fp, fp, fp, fp, f32, fp, fp, vp]),
+    "ustrun_bn_eval_consts": (i32, [i32, fp, fp, fp, fp, f32, fp, vp]),
     "ustrun_bn_relu_apply": (i32, [vp, fp, fp, i64, i32, i32, fp, i32, i32, vp]),
     "ustrun_pool_act": (i32, [PSrc, i32, vp, i32, vp]),
     "ustrun_pool_act2": (i32, [PSrc, i32, vp, vp, i32, vp]),
@@ -71,6 +72,8 @@ SIGNATURES = {
     "ustrun_bn_bwd_partials_bytes": (i64, [i64, i32]),
     "ustrun_bn_bwd_reduce": (i32, [vp, vp, vp, fp, fp, fp, fp, fp, i32, i32, i32, i32, fp, fp, i32, fp, fp, i64, i32, vp]),
     "ustrun_bn_bwd_apply": (i32, [vp, vp, vp, fp, fp, fp, i32, i32, i32, i32, vp, i32, vp]),
+    "ustrun_bn_bwd_frozen": (i32, [vp, vp, vp, fp, fp, fp, fp, i32, i32, i32, i32, vp, fp, fp, i32, fp, i64, i32, vp]),
+    "ustrun_bn_bwd_frozen_passes": (i32, [vp, vp, vp, fp, fp, fp, fp, i32, i32, i32, i32, vp, fp, fp, i32, fp, i64, i32, i32, i64, vp]),
     "ustrun_bn_bwd_apply_head": (i32, [fp, fp, vp, fp, fp, fp, i32, i32, i32, i32, i32, vp, i32, i32, i64, vp]),
     "ustrun_conv3x3_dgrad": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "ustrun_conv3x3_dgrad_bnsum": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, fp, fp, i32, i64, fp, C.POINTER(i32), i32, vp]),

@@ -62,20 +62,27 @@ def _conv_bn_fwd(srcs, nsrc, wf, N, H, W, bn, train):
     else:
         L.check(lib.ustrun_conv3x3_fwd(srcs, nsrc, wf.data_ptr(), N, H, W, Cout, y.data_ptr(), None, DT, stream_ptr()),
                 "conv3x3_fwd")
-        L.check(lib.ustrun_bn_eval_affine(Cout, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                                          bn.running_var.data_ptr(), float(bn.eps), aff[0].data_ptr(), aff[1].data_ptr(),
-                                          stream_ptr()), "bn_eval_affine")
+        # (scale / shift as ustrun_bn_eval_affine forms them, and running_mean / rstd behind them for the eval-mode backward)
+        L.check(lib.ustrun_bn_eval_consts(Cout, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                                          bn.running_var.data_ptr(), float(bn.eps), aff.data_ptr(), stream_ptr()), "bn_eval_consts")
     return y, aff
 
 
-def _bn_bwd(da, y, aff, bn, N, H, W):
-    """dy (grad wrt the raw conv output) from da (grad wrt the activated output); returns dy, dgamma, dbeta"""
+def _bn_bwd(da, y, aff, bn, N, H, W, train=True):
+    """dy (grad wrt the raw conv output) from da (grad wrt the activated output); returns dy, dgamma, dbeta.  train=False: through
+    the frozen statistics of eval mode (aff = the running constants), one pass"""
     lib = L.lib()
     Cc = bn.num_features
     dg, db = torch.empty(Cc, device=da.device), torch.empty(Cc, device=da.device)
-    coef = torch.empty(3, Cc, device=da.device)
     nb = lib.ustrun_bn_bwd_partials_bytes(N * H * W, Cc)
     part = torch.empty(nb // 4, device=da.device)
+    if not train:
+        dy = torch.empty_like(da)
+        L.check(lib.ustrun_bn_bwd_frozen(da.data_ptr(), None, y.data_ptr(), aff[0].data_ptr(), aff[1].data_ptr(), aff[2].data_ptr(),
+                                         aff[3].data_ptr(), N, H, W, Cc, dy.data_ptr(), dg.data_ptr(), db.data_ptr(), 0,
+                                         part.data_ptr(), nb, DT, stream_ptr()), "bn_bwd_frozen")
+        return dy, dg, db
+    coef = torch.empty(3, Cc, device=da.device)
     L.check(lib.ustrun_bn_bwd_reduce(da.data_ptr(), None, y.data_ptr(), aff[0].data_ptr(), aff[1].data_ptr(), aff[2].data_ptr(),
                                      aff[3].data_ptr(), bn.weight.data_ptr(), N, H, W, Cc, dg.data_ptr(), db.data_ptr(), 0,
                                      coef.data_ptr(), part.data_ptr(), nb, DT, stream_ptr()), "bn_bwd_reduce")
@@ -141,8 +148,6 @@ class _DoubleConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        if not ctx.train:
-            raise NotImplementedError("backward through eval-mode BatchNorm is not built (the reference never needs it)")
         lib = L.lib()
         dc = ctx.module.double_conv
         c1, b1, c2, b2 = dc[0], dc[1], dc[3], dc[4]
@@ -150,13 +155,13 @@ class _DoubleConvFn(torch.autograd.Function):
         N, H, W, Cx = ph.shape
         Cm, Co = b1.num_features, b2.num_features
         da2 = _nhwc(_f32c(dout, "grad"))
-        dy2, dg2, db2 = _bn_bwd(da2, y2, aff2, b2, N, H, W)
+        dy2, dg2, db2 = _bn_bwd(da2, y2, aff2, b2, N, H, W, ctx.train)
         s1 = _one(L.nhwc_src(y1.data_ptr(), Cm, H, W, scale=aff1[0].data_ptr(), shift=aff1[1].data_ptr(), relu=1))
         dw2 = _wgrad3(s1, 1, dy2, N, H, W, Cm, Co)
         da1 = torch.empty(N, H, W, Cm, device=dout.device)
         L.check(lib.ustrun_conv3x3_dgrad(dy2.data_ptr(), wd2.data_ptr(), N, H, W, Co, Cm, da1.data_ptr(), Cm, None, 0, 0, 0, 0, DT,
                                          stream_ptr()), "conv3x3_dgrad")
-        dy1, dg1, db1 = _bn_bwd(da1, y1, aff1, b1, N, H, W)
+        dy1, dg1, db1 = _bn_bwd(da1, y1, aff1, b1, N, H, W, ctx.train)
         if up is not None:
             uh, uw = up.shape[1], up.shape[2]
             srcs = (L.Src * 2)()

@@ -163,7 +163,12 @@ class _UNetFn(torch.autograd.Function):
         dx = torch.empty_like(ctx.x) if ctx.needs_input_grad[0] else None
         params = model_params(model)
         sink = getattr(model, "_ustrun_grad_sink", None)
-        if sink is not None:
+        # no parameter wants a gradient (saliency, an adversarial / VAT perturbation against a frozen network): grads = NULL, the
+        # backward launches no weight gradient and no dgamma / dbeta -- in eval mode no BatchNorm sum at all
+        input_only = sink is None and not any(ctx.needs_input_grad[6:])
+        if input_only:
+            targets, accumulate = None, 0
+        elif sink is not None:
             targets, accumulate = sink, 0 if getattr(model, "_ustrun_sink_fresh", True) else 1
             model._ustrun_sink_fresh = False
         else:
@@ -173,7 +178,7 @@ class _UNetFn(torch.autograd.Function):
                 targets.append(flat[o:o + p.numel()].view_as(p))
                 o += p.numel()
             accumulate = 0
-        arr = (C.c_void_p * len(targets))(*[t.data_ptr() for t in targets])
+        arr = None if input_only else (C.c_void_p * len(targets))(*[t.data_ptr() for t in targets])
         split = getattr(model, "_ustrun_backward_split_hook", None)
 
         def run(part):      # (null dfeat and dx: launch for launch ustrun_unet_backward / _part, which forward here with nulls)
@@ -192,7 +197,7 @@ class _UNetFn(torch.autograd.Function):
                 elif part == 3:
                     mid()
         ctx.ws = None
-        grads = (None,) * ctx.nparams if sink is not None else tuple(targets)
+        grads = (None,) * ctx.nparams if sink is not None or input_only else tuple(targets)
         return (dx, None, None, None, None, None) + grads
 
 
@@ -233,11 +238,15 @@ def unet_forward(model, x, feature=False, groups=1, tail=0, lead=0):
     logits' gradient are ignored): a no-grad forward that must come first in BatchNorm order rides in the same call."""
     params = model_params(model)
     wants_dx = torch.is_grad_enabled() and x.requires_grad
-    if wants_dx and not model.training:
-        raise NotImplementedError("UNet: the eval-mode backward (running statistics) is not built: gradient w.r.t. the network "
-                                  "input needs model.train()")
-    # (the node is recorded for the input alone too: every parameter frozen, x.requires_grad -- adversarial perturbation, saliency)
-    needs_grad = torch.is_grad_enabled() and model.training and (wants_dx or any(p.requires_grad for p in params))
+    # eval mode records the node only for a model that asks for it (model.eval_backward = True): without it an eval-mode call does
+    # what it always did -- no node, the workspace freed on return -- and an input that wants a gradient is refused, not ignored
+    differentiable = model.training or getattr(model, "eval_backward", False)
+    if wants_dx and not differentiable:
+        raise NotImplementedError("UNet: the eval-mode backward (running statistics) is switched off for this model: set "
+                                  "model.eval_backward = True for gradients through the frozen BatchNorm, or call model.train()")
+    # (the node is recorded for the input alone too: every parameter frozen, x.requires_grad -- adversarial perturbation, saliency;
+    # in eval mode the descriptor carries train = 0 and the backward goes through the frozen BatchNorm, the running buffers untouched)
+    needs_grad = torch.is_grad_enabled() and differentiable and (wants_dx or any(p.requires_grad for p in params))
     if needs_grad:
         return _UNetFn.apply(x, model, feature, groups, tail, lead, *params)
     logits, feat, _, _ = _run_forward(model, x, feature, groups, tail, lead)
