@@ -603,6 +603,7 @@ extern "C" int ustrun_pseudo_label(const float* logits, int N, int K, int HW, fl
                                    float* mask, ustrun_stream_t s) {
     USTRUN_CHECK(logits && label && mask, "pseudo_label: null pointer");
     USTRUN_CHECK(K >= 1 && K <= KMAX && N > 0 && HW > 0 && (long)N * HW < (1L << 32), "pseudo_label: bad shape");
+    USTRUN_CHECK(mode == USTRUN_LOSS_SOFTMAX || mode == USTRUN_LOSS_SIGMOID, "pseudo_label: bad mode %d", mode);
     const long items = mode == USTRUN_LOSS_SOFTMAX ? (long)N * HW : (long)N * K * HW;
     hipLaunchKernelGGL(pseudo_label_kernel, dim3(stream_blocks(items)), dim3(256), 0, (hipStream_t)s, logits, N, K, HW,
                        threshold, mode, label, mask);
@@ -617,6 +618,8 @@ extern "C" int ustrun_mix_targets(int mode, int N, int K, int HW, const float* b
                                   ustrun_stream_t s) {
     USTRUN_CHECK(box && pl && mask && pl_w_ul && mask_w_ul && pl_w_lu && mask_w_lu && cut_label && cut_mask && pl_w &&
                      mask_w && pl_ul && mask_ul && pl_lu && mask_lu, "mix_targets: null pointer");
+    USTRUN_CHECK(mode == USTRUN_LOSS_SOFTMAX || mode == USTRUN_LOSS_SIGMOID, "mix_targets: bad mode %d", mode);
+    USTRUN_CHECK(K >= 1 && K <= KMAX && N > 0 && HW > 0, "mix_targets: bad shape N=%d K=%d HW=%d", N, K, HW);
     const long items = (long)N * (mode == USTRUN_LOSS_SOFTMAX ? 1 : K) * HW;
     hipLaunchKernelGGL(mix_targets_kernel, dim3(stream_blocks(items)), dim3(256), 0, (hipStream_t)s, mode, N, K, HW, box,
                        pl, mask, pl_w_ul, mask_w_ul, pl_w_lu, mask_w_lu, cut_label, cut_mask, pl_w, mask_w, pl_ul,
