@@ -84,7 +84,7 @@ SHAPES = [(1, 1, 1, False), (2, 16, 16, False), (3, 5, 7, False), (2, 5, 7, True
 @pytest.mark.parametrize("dtype", ["f32", "bf16", "f16"])
 def test_operator_exact_on_small_integers(dtype, n, h, w, pooled):
     g = torch.Generator().manual_seed(500 + 31 * h + w)
-    for c in (4, 8, 24, 64, 256):
+    for c in (4, 8, 24, 64, 256, 1032):
         for with_da in ((True, False) if pooled else (True,)):
             da, dp, y, consts = _integer_case(n, h, w, c, pooled, dtype, g, with_da)
             dy, dg, db, _ = frozen(da, dp, y, consts, dtype)

@@ -157,7 +157,9 @@ def test_convT2x2_fwd_bwd(n, ci, co, h, w):
 
 
 @pytest.mark.parametrize("n,c,h,w,pool", [(2, 512, 4, 4, False), (2, 64, 16, 16, True), (1, 24, 9, 7, True),
-                                          (3, 128, 6, 10, False), (2, 1024, 2, 2, False), (2, 512, 4, 4, True)])
+                                          (3, 128, 6, 10, False), (2, 1024, 2, 2, False), (2, 512, 4, 4, True),
+                                          # C / 4 = 258 > G = 256: a second channel round whose upper 254 lanes idle through the barriers
+                                          (1, 1032, 3, 5, False), (1, 1032, 4, 6, True)])
 def test_bn_relu_pool_backward(n, c, h, w, pool):
     """BatchNorm(train)+ReLU(+MaxPool) backward against torch autograd of the same expression."""
     l = L()
@@ -739,6 +741,8 @@ def test_bf16_storage_bn_head_backward():
     (2, 64, 12, 16, True, 0),         # pooled windows of an even-sized map (no validity selects)
     (2, 128, 10, 14, True, 0),
     (2, 64, 11, 15, True, 0),         # odd-sized map: the general pooled form
+    (1, 1032, 4, 6, True, 0),         # C / 4 = 258 > G = 256: two channel rounds, 254 lanes idle in the second
+    (1, 1032, 3, 5, False, 0),        # ... plain: 129 octets, not a power of two -> the 4-channel kernels
 ])
 def test_bn_backward_bf16_builds(n, c, h, w, pool, flags):
     """Every build of the BatchNorm + ReLU (+ MaxPool routing) backward on bf16 tensors: against torch autograd in float64 through

@@ -4,6 +4,7 @@
 // reproducible run to run.
 #include "common.h"
 #include "loader.h"
+#include "bn_bwd.h"
 
 namespace ustrun {
 namespace {
@@ -430,607 +431,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restric
 }
 
 // ---- backward -------------------------------------------------------------------------------
-// One "window" = one pixel (POOL = false) or one 2x2 pooling window (POOL = true).  For each
-// element: a = relu(s*y+b); da_total = da + (dp routed to the window's first arg-max of a);
-// dz = da_total * (a > 0).
-template <bool POOL>
-struct Win {
-    static constexpr int NPX = POOL ? 4 : 1;
-};
-
-// EVEN (pooled windows of an even-sized map: every U-Net level): all four pixels and the pooled cell exist, so the validity
-// selects (3 per element), the clamped addresses and the integer arg-max index go away -- the routing is three compares per channel
-// and mask logic.  The general form below costs 360 VALU instructions per window for 72 loaded bytes: the pooled reduce was issue
-// bound at 3.3 TB/s (profiles/r03_bench_bn_bwd.log).
-template <bool POOL, int ESZ, bool EVEN = false>
-__device__ __forceinline__ void window_dz(const float* da, const float* __restrict__ dp,
-                                          const float* __restrict__ y, f32x4 sc, f32x4 sh, long w, int WH, int WW,
-                                          int H, int W, int C, int c, f32x4 (&yv)[Win<POOL>::NPX],
-                                          f32x4 (&dz)[Win<POOL>::NPX], bool (&ok)[Win<POOL>::NPX]) {
-    constexpr int NPX = Win<POOL>::NPX;
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    f32x4 av[NPX];
-    if constexpr (POOL && EVEN) {
-        const unsigned uw = (unsigned)w, per = (unsigned)(WH * WW);
-        const unsigned n = uw / per, rem = uw - n * per, wy = rem / (unsigned)WW, wx = rem - wy * (unsigned)WW;
-        const long off0 = (((long)n * H + 2 * wy) * W + 2 * wx) * C + c;
-        const long rowo = (long)W * C;
-        yv[0] = ld4t<ESZ>(y, off0); yv[1] = ld4t<ESZ>(y, off0 + C); yv[2] = ld4t<ESZ>(y, off0 + rowo); yv[3] = ld4t<ESZ>(y, off0 + rowo + C);
-        if (da) {
-            dz[0] = ld4t<ESZ>(da, off0); dz[1] = ld4t<ESZ>(da, off0 + C); dz[2] = ld4t<ESZ>(da, off0 + rowo); dz[3] = ld4t<ESZ>(da, off0 + rowo + C);
-        } else {
-            dz[0] = dz[1] = dz[2] = dz[3] = zero;
-        }
-        const f32x4 g4 = dp ? ld4t<ESZ>(dp, (long)w * C + c) : zero;       // the pooled map's cell IS window w
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { ok[q] = true; av[q] = yv[q] * sc + sh; }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            // first arg-max of relu(a) in the order (0,0) (0,1) (1,0) (1,1): strict > keeps the first
-            const float a0 = fmaxf(av[0][j], 0.f), a1 = fmaxf(av[1][j], 0.f), a2 = fmaxf(av[2][j], 0.f), a3 = fmaxf(av[3][j], 0.f);
-            const bool m1 = a1 > a0;
-            const float b1 = fmaxf(a0, a1);
-            const bool m2 = a2 > b1;
-            const float b2 = fmaxf(b1, a2);
-            const bool m3 = a3 > b2;
-            const float g = g4[j];
-            const bool e3 = m3, e2 = m2 && !m3, e1 = m1 && !m2 && !m3, e0 = !(m1 || m2 || m3);
-            dz[0][j] += e0 ? g : 0.f; dz[1][j] += e1 ? g : 0.f; dz[2][j] += e2 ? g : 0.f; dz[3][j] += e3 ? g : 0.f;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dz[q][j] = (av[q][j] > 0.f) ? dz[q][j] : 0.f;
-        return;
-    }
-    // plain: the window IS the pixel, its offset is linear (no division: these kernels were instruction bound on the
-    // 64-bit divides, not memory bound); pooled: 32-bit divides (windows per pass < 2^31)
-    int n = 0, wy = 0, wx = 0;
-    if (POOL) {
-        const unsigned uw = (unsigned)w, per = (unsigned)(WH * WW);
-        n = (int)(uw / per);
-        const unsigned rem = uw - (unsigned)n * per;
-        wy = (int)(rem / (unsigned)WW); wx = (int)(rem - (unsigned)wy * (unsigned)WW);
-    }
-    // every load of the window is issued unconditionally (out-of-range pixels read the window's first pixel, always
-    // inside, and are zeroed afterwards): nine independent loads in flight instead of one masked region after another
-    const long off0 = POOL ? (((long)n * H + 2 * wy) * W + 2 * wx) * C + c : w * C + c;
-#pragma unroll
-    for (int q = 0; q < NPX; ++q) {
-        const int py = 2 * wy + (q >> 1), px = 2 * wx + (q & 1);
-        ok[q] = !POOL || (py < H && px < W);
-        const long off = ok[q] ? off0 + ((long)(q >> 1) * W + (q & 1)) * C : off0;
-        yv[q] = ld4t<ESZ>(y, off);
-        if constexpr (POOL) dz[q] = da ? ld4t<ESZ>(da, off) : zero;      // (pooled layers may have no direct consumer)
-        else dz[q] = ld4t<ESZ>(da, off);                                  // plain: da is always there -- no branch around the load
-    }
-    f32x4 gpool = zero;
-    bool gok = false;
-    if (POOL && dp) {
-        const int PH = H / 2, PW = W / 2;
-        gok = wy < PH && wx < PW;
-        gpool = ld4t<ESZ>(dp, (((long)n * PH + (gok ? wy : 0)) * PW + (gok ? wx : 0)) * C + c);
-    }
-    // everything below is selects, not branches (the compiler turned the arg-max routing into ~40 exec-mask regions)
-#pragma unroll
-    for (int q = 0; q < NPX; ++q) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            yv[q][j] = ok[q] ? yv[q][j] : 0.f;
-            dz[q][j] = ok[q] ? dz[q][j] : 0.f;
-            av[q][j] = ok[q] ? yv[q][j] * sc[j] + sh[j] : 0.f;
-        }
-    }
-    if (POOL) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float g = gok ? gpool[j] : 0.f;
-            // first arg-max of relu(a) over the window, in the order (0,0) (0,1) (1,0) (1,1): strict > keeps the first
-            const float a0 = fmaxf(av[0][j], 0.f), a1 = fmaxf(av[1][j], 0.f), a2 = fmaxf(av[2][j], 0.f), a3 = fmaxf(av[3][j], 0.f);
-            const bool m1 = a1 > a0;
-            const float b1 = m1 ? a1 : a0;
-            const bool m2 = a2 > b1;
-            const float b2 = m2 ? a2 : b1;
-            const bool m3 = a3 > b2;
-            const int best = m3 ? 3 : (m2 ? 2 : (m1 ? 1 : 0));
-#pragma unroll
-            for (int q = 0; q < NPX; ++q) dz[q][j] += (q == best) ? g : 0.f;
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < NPX; ++q)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dz[q][j] = (av[q][j] > 0.f) ? dz[q][j] : 0.f;
-}
-
-// grid-stride over windows; thread = (channel quad, window lane).  partials[block][2][C]
-// blockIdx.y = forward pass (batched passes: each has its own slice of every tensor, constants and partial rows)
-struct PassOff { long act, pool, aff, part, coef; };   // element strides between passes (bytes are esz * act for tensors)
-
-template <bool POOL, int ESZ, bool EVEN = false>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ da, const float* __restrict__ dp,
-                                                           const float* __restrict__ y, const float* __restrict__ scale,
-                                                           const float* __restrict__ shift, int N, int H, int W, int C,
-                                                           int G, float* __restrict__ partials, const PassOff po) {
-    constexpr int NPX = Win<POOL>::NPX;
-    {
-        const long g = blockIdx.y;
-        if (da) da = (const float*)((const char*)da + g * po.act * ESZ);
-        if (dp) dp = (const float*)((const char*)dp + g * po.pool * ESZ);
-        y = (const float*)((const char*)y + g * po.act * ESZ);
-        scale += g * po.aff; shift += g * po.aff; partials += g * po.part;
-    }
-    __shared__ f32x4 red[2][256];
-    const int C4 = C / 4, PL = 256 / G;
-    const int cq0 = threadIdx.x % G, pl = threadIdx.x / G;
-    const int WH = POOL ? (H + 1) / 2 : H, WW = POOL ? (W + 1) / 2 : W;
-    const long nwin = (long)N * WH * WW;
-    for (int cb = 0; cb < C4; cb += G) {      // uniform trip count: the body holds barriers
-        const int cq = cb + cq0;
-        const bool active = cq < C4;
-        const int c = active ? cq * 4 : 0;
-        const f32x4 sc = *(const f32x4*)(scale + c), sh = *(const f32x4*)(shift + c);
-        f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
-        if (active) {
-            // plain path: four windows per trip, their eight loads issued before the first use (one window per trip left the
-            // memory-level parallelism to occupancy alone: 4.7 -> 5.2 TB/s; eight per trip: no further gain); the sums still run in ascending window order
-            constexpr int U = POOL ? 1 : 4;
-            const long stride = (long)gridDim.x * PL;
-            long w = (long)blockIdx.x * PL + pl;
-            for (; w + (U - 1) * stride < nwin; w += U * stride) {
-                f32x4 yv[U][NPX], dz[U][NPX]; bool ok[U][NPX];
-#pragma unroll
-                for (int u = 0; u < U; ++u) window_dz<POOL, ESZ, EVEN>(da, dp, y, sc, sh, w + u * stride, WH, WW, H, W, C, c, yv[u], dz[u], ok[u]);
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int q = 0; q < NPX; ++q) { s1 += dz[u][q]; s2 += dz[u][q] * yv[u][q]; }
-            }
-            for (; w < nwin; w += stride) {
-                f32x4 yv[NPX], dz[NPX]; bool ok[NPX];
-                window_dz<POOL, ESZ, EVEN>(da, dp, y, sc, sh, w, WH, WW, H, W, C, c, yv, dz, ok);
-#pragma unroll
-                for (int q = 0; q < NPX; ++q) { s1 += dz[q]; s2 += dz[q] * yv[q]; }
-            }
-        }
-        red[0][threadIdx.x] = s1; red[1][threadIdx.x] = s2;
-        __syncthreads();
-        if (pl == 0 && active) {
-            for (int k = 1; k < PL; ++k) { s1 += red[0][k * G + cq0]; s2 += red[1][k * G + cq0]; }
-            *(f32x4*)(partials + ((long)blockIdx.x * 2 + 0) * C + c) = s1;
-            *(f32x4*)(partials + ((long)blockIdx.x * 2 + 1) * C + c) = s2;
-        }
-        __syncthreads();
-    }
-}
-
-// partials[pass][rows][2][C] -> dgamma, dbeta (the passes' contributions added one after the other, as separate calls
-// would), coef[pass][3][C]
-template <bool PRE>
-__global__ void bn_bwd_finalize_kernel(const float* __restrict__ partials, int rows, int C, double count,
-                                       const float* __restrict__ gamma, const float* __restrict__ mean,
-                                       const float* __restrict__ rstd, float* dgamma, float* dbeta, int accumulate,
-                                       float* coef, int passes, const PassOff po, long rstride, long roff, int R) {
-    __shared__ double red[2][32][32];
-    const int cl = threadIdx.x & 31, rg = threadIdx.x >> 5;      // 32 channels x 32 row lanes
-    const int c = blockIdx.x * 32 + cl;
-    float dg_run = 0.f, db_run = 0.f;
-    if (rg == 0 && c < C && dgamma && accumulate) { dg_run = dgamma[c]; db_run = dbeta[c]; }
-    // up to four passes per round, eight row lanes each (as bn_finalize_kernel: the passes' sums are independent, only the
-    // dgamma/dbeta accumulation is sequential; a pass's sums are formed in the same order alone or batched)
-    constexpr int LPP = 8, PPR = 32 / LPP;
-    const int gl = rg / LPP, lane = rg % LPP;
-    for (int g0 = 0; g0 < passes; g0 += PPR) {
-        const int g = g0 + gl;
-        double s1 = 0.0, s2 = 0.0;
-        if (c < C && g < passes) {
-            const float* pt = partials + (long)g * po.part + roff + c;
-            if constexpr (PRE) {     // rows of a convolution's epilogue, pre-reduced in place by bn_stat_stage1_kernel: f64 sums parked as
-                                     // (hi, lo) float pairs at rows sp*R (sum 1) and sp*R+1 (sum 2); at most 32 splits = four per lane
-                float v[4][4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int sp = lane + LPP * k;
-                    const bool ok = sp * R < rows;
-                    const long a0 = ok ? (long)(sp * R) * 2 * C : 0, a1 = ok ? (long)(sp * R + 1) * 2 * C : 0;
-                    const float x0 = pt[a0], x1 = pt[a0 + C], x2 = pt[a1], x3 = pt[a1 + C];
-                    v[k][0] = ok ? x0 : 0.f; v[k][1] = ok ? x1 : 0.f; v[k][2] = ok ? x2 : 0.f; v[k][3] = ok ? x3 : 0.f;
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { s1 += (double)v[k][0] + (double)v[k][1]; s2 += (double)v[k][2] + (double)v[k][3]; }
-            }
-            int r = PRE ? rows : lane;
-            for (; r + 7 * LPP < rows; r += 8 * LPP) {       // eight rows' loads issued before the first sum (written out: left
-                float a[8], b[8];                            // to the unroller, each load was waited for on its own)
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { const float* q = pt + (long)(r + u * LPP) * rstride; a[u] = q[0]; b[u] = q[C]; }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { s1 += (double)a[u]; s2 += (double)b[u]; }
-            }
-            for (; r < rows; r += LPP) {
-                s1 += (double)pt[(long)r * rstride];
-                s2 += (double)pt[(long)r * rstride + C];
-            }
-        }
-        red[0][rg][cl] = s1; red[1][rg][cl] = s2;
-        __syncthreads();
-        if (rg == 0 && c < C) {
-            for (int q = 0; q < PPR && g0 + q < passes; ++q) {
-                double t1 = 0.0, t2 = 0.0;
-                for (int k = 0; k < LPP; ++k) { t1 += red[0][q * LPP + k][cl]; t2 += red[1][q * LPP + k][cl]; }
-                const int gq = g0 + q;
-                const double mu = mean[(long)gq * po.aff + c], rs = rstd[(long)gq * po.aff + c], gm = gamma[c];
-                const double dbe = t1, dga = rs * (t2 - mu * t1);
-                const double c0 = gm * rs, m1 = dbe / count, m2 = dga / count;
-                const double c1 = -c0 * m2 * rs, c2 = -c0 * m1 - c1 * mu;
-                float* cf = coef + (long)gq * po.coef;
-                cf[c] = (float)c0; cf[C + c] = (float)c1; cf[2 * C + c] = (float)c2;
-                if (gq == 0 && !accumulate) { dg_run = (float)dga; db_run = (float)dbe; }
-                else { dg_run = dg_run + (float)dga; db_run = db_run + (float)dbe; }
-            }
-        }
-        __syncthreads();
-    }
-    if (rg == 0 && c < C && dgamma) { dgamma[c] = dg_run; dbeta[c] = db_run; }
-}
-
-template <bool POOL, int ESZ, bool EVEN = false>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* da, const float* __restrict__ dp,
-                                                          const float* __restrict__ y, const float* __restrict__ scale,
-                                                          const float* __restrict__ shift, const float* __restrict__ coef,
-                                                          int N, int H, int W, int C, int G, float* dy, const PassOff po) {
-    constexpr int NPX = Win<POOL>::NPX;
-    {
-        const long g = blockIdx.y;
-        if (da) da = (const float*)((const char*)da + g * po.act * ESZ);
-        if (dp) dp = (const float*)((const char*)dp + g * po.pool * ESZ);
-        y = (const float*)((const char*)y + g * po.act * ESZ);
-        dy = (float*)((char*)dy + g * po.act * ESZ);
-        scale += g * po.aff; shift += g * po.aff; coef += g * po.coef;
-    }
-    const int C4 = C / 4, PL = 256 / G;
-    const int cq0 = threadIdx.x % G, pl = threadIdx.x / G;
-    const int WH = POOL ? (H + 1) / 2 : H, WW = POOL ? (W + 1) / 2 : W;
-    const long nwin = (long)N * WH * WW;
-    for (int cq = cq0; cq < C4; cq += G) {
-        const int c = cq * 4;
-        const f32x4 sc = *(const f32x4*)(scale + c), sh = *(const f32x4*)(shift + c);
-        const f32x4 k0 = *(const f32x4*)(coef + c), k1 = *(const f32x4*)(coef + C + c), k2 = *(const f32x4*)(coef + 2 * C + c);
-        // (one window per trip here: with four the loads and the four stores of a trip queue behind each other -- measured
-        // 110 -> 125 us, while the store-free reduce gained 13 % from the same change)
-        const long stride = (long)gridDim.x * PL;
-        long w = (long)blockIdx.x * PL + pl;
-        for (; w < nwin; w += stride) {
-            f32x4 yv[NPX], dz[NPX]; bool ok[NPX];
-            window_dz<POOL, ESZ, EVEN>(da, dp, y, sc, sh, w, WH, WW, H, W, C, c, yv, dz, ok);
-            long base = w * C + c;                       // plain: the pixel itself
-            if (POOL) {
-                const unsigned uw = (unsigned)w, per = (unsigned)(WH * WW);
-                const unsigned n = uw / per, rem = uw - n * per, wy = rem / (unsigned)WW, wx = rem - wy * (unsigned)WW;
-                base = (((long)n * H + 2 * wy) * W + 2 * wx) * C + c;
-            }
-#pragma unroll
-            for (int q = 0; q < NPX; ++q) {
-                if (!ok[q]) continue;
-                st4t<ESZ>(dy, base + ((long)(q >> 1) * W + (q & 1)) * C, k0 * dz[q] + k1 * yv[q] + k2);
-            }
-        }
-    }
-}
-
-// ---- plain (un-pooled) bf16 passes with 8 channels = 16 bytes per lane (round 3) --------------------------------------------
-// The 4-channel kernels above keep 16 bytes per thread in flight (two 8-byte loads, one pixel per trip in the apply pass): at
-// their occupancy that is about half of what 8 TB/s x the memory latency asks of a CU, and the plain apply pass ran at
-// 4.8-5.1 TB/s where the pooled one (nine loads per thread) reaches 5.5.  Here a lane owns 8 channels of a pixel: thread =
-// (octet tid % G8, pixel lane tid / G8), G8 = C / 8 a power of two <= 256; the arithmetic is the same per element.
-// (F8, up8, ld8f and the apply statement bn_bwd_apply8 live in common.h: the first convolution's weight gradient uses them too)
-__global__ __launch_bounds__(256) void bn_bwd_apply_x8_kernel(const elt_t* __restrict__ da, const elt_t* __restrict__ y,
-                                                             const float* __restrict__ scale, const float* __restrict__ shift,
-                                                             const float* __restrict__ coef, long npix, int C, int G8,
-                                                             elt_t* __restrict__ dy, const PassOff po) {
-    {
-        const long g = blockIdx.y;
-        da += g * po.act; y += g * po.act; dy += g * po.act;
-        scale += g * po.aff; shift += g * po.aff; coef += g * po.coef;
-    }
-    const int PL = 256 / G8;
-    const int c = 8 * (threadIdx.x % G8), pl = threadIdx.x / G8;
-    const F8 sc = ld8f(scale + c), sh = ld8f(shift + c), k0 = ld8f(coef + c), k1 = ld8f(coef + C + c), k2 = ld8f(coef + 2 * C + c);
-    const long stride = (long)gridDim.x * PL;
-    constexpr int U = 2;
-    long w = (long)blockIdx.x * PL + pl;
-    auto one = [&](bf16x8 yb, bf16x8 db) { return bn_bwd_apply8(yb, db, sc, sh, k0, k1, k2); };
-    for (; w + (U - 1) * stride < npix; w += U * stride) {
-        bf16x8 yb[U], db[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) { yb[u] = *(const bf16x8*)(y + (w + u * stride) * C + c); db[u] = *(const bf16x8*)(da + (w + u * stride) * C + c); }
-#pragma unroll
-        for (int u = 0; u < U; ++u) *(bf16x8*)(dy + (w + u * stride) * C + c) = one(yb[u], db[u]);
-    }
-    for (; w < npix; w += stride)
-        *(bf16x8*)(dy + w * C + c) = one(*(const bf16x8*)(y + w * C + c), *(const bf16x8*)(da + w * C + c));
-}
-
-// The same pass for the layer under the head, whose da nobody stored: da[p][c] = sum_k dl[k][p] w[k][c] is formed again from the K
-// f32 values of dl per pixel (8 B at K = 2, against 128 B of stored gradient) exactly as head_bwd_kernel forms it -- head_grad4,
-// rounded to the storage type as its store rounds it -- and goes through bn_bwd_apply8 like a loaded one.  dl is NCHW: dl[(n K + k) HW
-// + hw]; a trip's first pixel is block-uniform, so the division by HW runs once per trip on the scalar unit and a lane only steps
-// over image ends.  KT > 0: the class count at compile time; KT == 0: any K <= HEAD_KMAX.
-constexpr int HEAD_KMAX = 8;
-template <int KT>
-__global__ __launch_bounds__(256) void bn_bwd_apply_head_x8_kernel(const float* __restrict__ dl, const float* __restrict__ w_head,
-                                                                  const elt_t* __restrict__ y, const float* __restrict__ scale,
-                                                                  const float* __restrict__ shift, const float* __restrict__ coef,
-                                                                  long npix, int HW, int C, int G8, int Krt, elt_t* __restrict__ dy,
-                                                                  const PassOff po) {
-    constexpr int KN = KT > 0 ? KT : HEAD_KMAX;
-    const int K = KT > 0 ? KT : Krt;
-    {
-        const long g = blockIdx.y;
-        dl += g * npix * K; y += g * po.act; dy += g * po.act;
-        scale += g * po.aff; shift += g * po.aff; coef += g * po.coef;
-    }
-    const int PL = 256 / G8;
-    const int c = 8 * (threadIdx.x % G8), pl = threadIdx.x / G8;
-    const F8 sc = ld8f(scale + c), sh = ld8f(shift + c), k0 = ld8f(coef + c), k1 = ld8f(coef + C + c), k2 = ld8f(coef + 2 * C + c);
-    f32x4 wlo[KN], whi[KN];
-#pragma unroll
-    for (int k = 0; k < KN; ++k) {
-        const bool on = KT > 0 || k < K;
-        wlo[k] = on ? *(const f32x4*)(w_head + k * C + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
-        whi[k] = on ? *(const f32x4*)(w_head + k * C + c + 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    const long stride = (long)gridDim.x * PL;
-    constexpr int U = 2;
-    // the K values of dl at pixel wb + pl (wb: the trip's first pixel, block-uniform)
-    auto load_d = [&](long wb, float (&d)[KN]) {
-        const unsigned n0 = (unsigned)wb / (unsigned)HW;              // npix < 2^31 (checked on the host)
-        long n = n0;
-        int hw = (int)(wb - (long)n0 * HW) + pl;
-        while (hw >= HW) { hw -= HW; ++n; }
-        const float* p = dl + n * K * HW + hw;
-#pragma unroll
-        for (int k = 0; k < KN; ++k) d[k] = (KT > 0 || k < K) ? p[(long)k * HW] : 0.f;
-    };
-    auto grad = [&](const float (&d)[KN]) {
-        const f32x4 lo = head_grad4<KN, KT == 0>(d, wlo, K), hi = head_grad4<KN, KT == 0>(d, whi, K);
-        bf16x8 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { o[j] = (elt_t)lo[j]; o[4 + j] = (elt_t)hi[j]; }
-        return o;
-    };
-    long wb = (long)blockIdx.x * PL;
-    for (; wb + pl + (U - 1) * stride < npix; wb += U * stride) {
-        bf16x8 yb[U]; float d[U][KN];
-#pragma unroll
-        for (int u = 0; u < U; ++u) { yb[u] = *(const bf16x8*)(y + (wb + pl + u * stride) * C + c); load_d(wb + u * stride, d[u]); }
-#pragma unroll
-        for (int u = 0; u < U; ++u) *(bf16x8*)(dy + (wb + pl + u * stride) * C + c) = bn_bwd_apply8(yb[u], grad(d[u]), sc, sh, k0, k1, k2);
-    }
-    for (; wb + pl < npix; wb += stride) {
-        float d[KN];
-        load_d(wb, d);
-        *(bf16x8*)(dy + (wb + pl) * C + c) = bn_bwd_apply8(*(const bf16x8*)(y + (wb + pl) * C + c), grad(d), sc, sh, k0, k1, k2);
-    }
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_reduce_x8_kernel(const elt_t* __restrict__ da, const elt_t* __restrict__ y,
-                                                              const float* __restrict__ scale, const float* __restrict__ shift,
-                                                              long npix, int C, int G8, float* __restrict__ partials,
-                                                              const PassOff po) {
-    {
-        const long g = blockIdx.y;
-        da += g * po.act; y += g * po.act;
-        scale += g * po.aff; shift += g * po.aff; partials += g * po.part;
-    }
-    __shared__ f32x4 red[4][256];
-    const int PL = 256 / G8;
-    const int g8 = threadIdx.x % G8, c = 8 * g8, pl = threadIdx.x / G8;
-    const F8 sc = ld8f(scale + c), sh = ld8f(shift + c);
-    F8 s1 = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, s2 = s1;
-    const long stride = (long)gridDim.x * PL;
-    constexpr int U = 4;
-    long w = (long)blockIdx.x * PL + pl;
-    auto acc1 = [&](bf16x8 yb, bf16x8 db) {
-        const F8 yv = up8(yb), dv = up8(db);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float al = yv.lo[j] * sc.lo[j] + sh.lo[j], ah = yv.hi[j] * sc.hi[j] + sh.hi[j];
-            const float zl = al > 0.f ? dv.lo[j] : 0.f, zh = ah > 0.f ? dv.hi[j] : 0.f;
-            s1.lo[j] += zl; s1.hi[j] += zh;
-            s2.lo[j] += zl * yv.lo[j]; s2.hi[j] += zh * yv.hi[j];
-        }
-    };
-    for (; w + (U - 1) * stride < npix; w += U * stride) {       // four pixels' loads in flight, sums in ascending pixel order
-        bf16x8 yb[U], db[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) { yb[u] = *(const bf16x8*)(y + (w + u * stride) * C + c); db[u] = *(const bf16x8*)(da + (w + u * stride) * C + c); }
-#pragma unroll
-        for (int u = 0; u < U; ++u) acc1(yb[u], db[u]);
-    }
-    for (; w < npix; w += stride) acc1(*(const bf16x8*)(y + w * C + c), *(const bf16x8*)(da + w * C + c));
-    red[0][threadIdx.x] = s1.lo; red[1][threadIdx.x] = s1.hi; red[2][threadIdx.x] = s2.lo; red[3][threadIdx.x] = s2.hi;
-    __syncthreads();
-    if (pl == 0) {                                              // fixed order over the block's pixel lanes
-        for (int k = 1; k < PL; ++k) {
-            s1.lo += red[0][k * G8 + g8]; s1.hi += red[1][k * G8 + g8];
-            s2.lo += red[2][k * G8 + g8]; s2.hi += red[3][k * G8 + g8];
-        }
-        float* r0 = partials + ((long)blockIdx.x * 2 + 0) * C + c;
-        float* r1 = partials + ((long)blockIdx.x * 2 + 1) * C + c;
-        *(f32x4*)r0 = s1.lo; *(f32x4*)(r0 + 4) = s1.hi;
-        *(f32x4*)r1 = s2.lo; *(f32x4*)(r1 + 4) = s2.hi;
-    }
-}
-
-// ---- frozen BatchNorm (running statistics): the backward in ONE pass ----------------------------------------------------------
-// With scale = gamma rstd and shift = beta - running_mean scale fixed, dy = scale g with g = (da [+ routed dp]) [y scale + shift > 0]
-// needs no batch sum: the apply pass does not wait for a reduce pass, and both read the same da, dp and y -- so one kernel reads
-// each once, writes dy (in place where dy == da: a thread owns its window's elements, loaded before they are stored) and, SUMS,
-// leaves the block's row {sum g, sum g y} for bn_bwd_frozen_finalize_kernel.  SUMS = false (frozen parameters): a pure apply pass,
-// no LDS, no row.  Thread = (channel quad, window lane) as in bn_bwd_reduce_kernel; one window per trip as in bn_bwd_apply_kernel
-// (loads and stores of several windows queue behind each other there).
-template <bool POOL, int ESZ, bool EVEN, bool SUMS>
-__global__ __launch_bounds__(256) void bn_bwd_frozen_kernel(const float* da, const float* __restrict__ dp, const float* __restrict__ y,
-                                                           const float* __restrict__ scale, const float* __restrict__ shift,
-                                                           int N, int H, int W, int C, int G, float* dy,
-                                                           float* __restrict__ partials, const PassOff po) {
-    constexpr int NPX = Win<POOL>::NPX;
-    {
-        const long g = blockIdx.y;
-        if (da) da = (const float*)((const char*)da + g * po.act * ESZ);
-        if (dp) dp = (const float*)((const char*)dp + g * po.pool * ESZ);
-        y = (const float*)((const char*)y + g * po.act * ESZ);
-        dy = (float*)((char*)dy + g * po.act * ESZ);
-        scale += g * po.aff; shift += g * po.aff;
-        if (SUMS) partials += g * po.part;
-    }
-    __shared__ f32x4 red[SUMS ? 2 : 1][SUMS ? 256 : 1];
-    const int C4 = C / 4, PL = 256 / G;
-    const int cq0 = threadIdx.x % G, pl = threadIdx.x / G;
-    const int WH = POOL ? (H + 1) / 2 : H, WW = POOL ? (W + 1) / 2 : W;
-    const long nwin = (long)N * WH * WW;
-    const long stride = (long)gridDim.x * PL;
-    for (int cb = 0; cb < C4; cb += G) {      // uniform trip count: with SUMS the body holds barriers
-        const int cq = cb + cq0;
-        const bool active = cq < C4;
-        const int c = active ? cq * 4 : 0;
-        const f32x4 sc = *(const f32x4*)(scale + c), sh = *(const f32x4*)(shift + c);
-        f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
-        if (active) {
-            for (long w = (long)blockIdx.x * PL + pl; w < nwin; w += stride) {
-                f32x4 yv[NPX], dz[NPX]; bool ok[NPX];
-                window_dz<POOL, ESZ, EVEN>(da, dp, y, sc, sh, w, WH, WW, H, W, C, c, yv, dz, ok);
-                long base = w * C + c;                       // plain: the pixel itself
-                if (POOL) {
-                    const unsigned uw = (unsigned)w, per = (unsigned)(WH * WW);
-                    const unsigned n = uw / per, rem = uw - n * per, wy = rem / (unsigned)WW, wx = rem - wy * (unsigned)WW;
-                    base = (((long)n * H + 2 * wy) * W + 2 * wx) * C + c;
-                }
-#pragma unroll
-                for (int q = 0; q < NPX; ++q) {
-                    if (SUMS) { s1 += dz[q]; s2 += dz[q] * yv[q]; }       // (pixels outside the map carry dz = y = 0)
-                    if (!ok[q]) continue;
-                    st4t<ESZ>(dy, base + ((long)(q >> 1) * W + (q & 1)) * C, sc * dz[q]);
-                }
-            }
-        }
-        if constexpr (SUMS) {
-            red[0][threadIdx.x] = s1; red[1][threadIdx.x] = s2;
-            __syncthreads();
-            if (pl == 0 && active) {                         // fixed order over the block's window lanes
-                for (int k = 1; k < PL; ++k) { s1 += red[0][k * G + cq0]; s2 += red[1][k * G + cq0]; }
-                *(f32x4*)(partials + ((long)blockIdx.x * 2 + 0) * C + c) = s1;
-                *(f32x4*)(partials + ((long)blockIdx.x * 2 + 1) * C + c) = s2;
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// The plain 16-bit form with 8 channels = 16 bytes per lane, two pixels in flight per trip (bn_bwd_apply_x8_kernel's shape; the
-// sums in ascending pixel order as bn_bwd_reduce_x8_kernel forms them)
-template <bool SUMS>
-__global__ __launch_bounds__(256) void bn_bwd_frozen_x8_kernel(const elt_t* da, const elt_t* __restrict__ y,
-                                                              const float* __restrict__ scale, const float* __restrict__ shift,
-                                                              long npix, int C, int G8, elt_t* dy, float* __restrict__ partials,
-                                                              const PassOff po) {
-    {
-        const long g = blockIdx.y;
-        da += g * po.act; y += g * po.act; dy += g * po.act;
-        scale += g * po.aff; shift += g * po.aff;
-        if (SUMS) partials += g * po.part;
-    }
-    __shared__ f32x4 red[SUMS ? 4 : 1][SUMS ? 256 : 1];
-    const int PL = 256 / G8;
-    const int g8 = threadIdx.x % G8, c = 8 * g8, pl = threadIdx.x / G8;
-    const F8 sc = ld8f(scale + c), sh = ld8f(shift + c);
-    F8 s1 = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, s2 = s1;
-    const long stride = (long)gridDim.x * PL;
-    constexpr int U = 2;
-    long w = (long)blockIdx.x * PL + pl;
-    auto one = [&](bf16x8 yb, bf16x8 db) {
-        const F8 yv = up8(yb), dv = up8(db);
-        bf16x8 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float al = yv.lo[j] * sc.lo[j] + sh.lo[j], ah = yv.hi[j] * sc.hi[j] + sh.hi[j];
-            const float zl = al > 0.f ? dv.lo[j] : 0.f, zh = ah > 0.f ? dv.hi[j] : 0.f;
-            if (SUMS) {
-                s1.lo[j] += zl; s1.hi[j] += zh;
-                s2.lo[j] += zl * yv.lo[j]; s2.hi[j] += zh * yv.hi[j];
-            }
-            o[j] = (elt_t)(sc.lo[j] * zl); o[4 + j] = (elt_t)(sc.hi[j] * zh);
-        }
-        return o;
-    };
-    for (; w + (U - 1) * stride < npix; w += U * stride) {
-        bf16x8 yb[U], db[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) { yb[u] = *(const bf16x8*)(y + (w + u * stride) * C + c); db[u] = *(const bf16x8*)(da + (w + u * stride) * C + c); }
-#pragma unroll
-        for (int u = 0; u < U; ++u) *(bf16x8*)(dy + (w + u * stride) * C + c) = one(yb[u], db[u]);
-    }
-    for (; w < npix; w += stride)
-        *(bf16x8*)(dy + w * C + c) = one(*(const bf16x8*)(y + w * C + c), *(const bf16x8*)(da + w * C + c));
-    if constexpr (SUMS) {
-        red[0][threadIdx.x] = s1.lo; red[1][threadIdx.x] = s1.hi; red[2][threadIdx.x] = s2.lo; red[3][threadIdx.x] = s2.hi;
-        __syncthreads();
-        if (pl == 0) {                                              // fixed order over the block's pixel lanes
-            for (int k = 1; k < PL; ++k) {
-                s1.lo += red[0][k * G8 + g8]; s1.hi += red[1][k * G8 + g8];
-                s2.lo += red[2][k * G8 + g8]; s2.hi += red[3][k * G8 + g8];
-            }
-            float* r0 = partials + ((long)blockIdx.x * 2 + 0) * C + c;
-            float* r1 = partials + ((long)blockIdx.x * 2 + 1) * C + c;
-            *(f32x4*)r0 = s1.lo; *(f32x4*)(r0 + 4) = s1.hi;
-            *(f32x4*)r1 = s2.lo; *(f32x4*)(r1 + 4) = s2.hi;
-        }
-    }
-}
-
-// partials[pass][rows][2][C] -> dbeta = sum g, dgamma = rstd (sum g y - running_mean sum g): the rows of a pass added in f64 on
-// eight row lanes in bn_bwd_finalize_kernel's order, the passes' contributions one after the other as separate calls would add
-// them.  No coefficient table: dy does not depend on the sums.
-__global__ void bn_bwd_frozen_finalize_kernel(const float* __restrict__ partials, int rows, int C, const float* __restrict__ mean,
-                                              const float* __restrict__ rstd, float* dgamma, float* dbeta, int accumulate,
-                                              int passes, const PassOff po) {
-    __shared__ double red[2][32][32];
-    const int cl = threadIdx.x & 31, rg = threadIdx.x >> 5;      // 32 channels x 32 row lanes
-    const int c = blockIdx.x * 32 + cl;
-    float dg_run = 0.f, db_run = 0.f;
-    if (rg == 0 && c < C && accumulate) { dg_run = dgamma[c]; db_run = dbeta[c]; }
-    constexpr int LPP = 8, PPR = 32 / LPP;
-    const int gl = rg / LPP, lane = rg % LPP;
-    for (int g0 = 0; g0 < passes; g0 += PPR) {
-        const int g = g0 + gl;
-        double s1 = 0.0, s2 = 0.0;
-        if (c < C && g < passes) {
-            const float* pt = partials + (long)g * po.part + c;
-#pragma unroll 8
-            for (int r = lane; r < rows; r += LPP) {
-                s1 += (double)pt[(long)r * 2 * C];
-                s2 += (double)pt[(long)r * 2 * C + C];
-            }
-        }
-        red[0][rg][cl] = s1; red[1][rg][cl] = s2;
-        __syncthreads();
-        if (rg == 0 && c < C) {
-            for (int q = 0; q < PPR && g0 + q < passes; ++q) {
-                double t1 = 0.0, t2 = 0.0;
-                for (int k = 0; k < LPP; ++k) { t1 += red[0][q * LPP + k][cl]; t2 += red[1][q * LPP + k][cl]; }
-                const int gq = g0 + q;
-                const double mu = mean[(long)gq * po.aff + c], rs = rstd[(long)gq * po.aff + c];
-                const double dbe = t1, dga = rs * (t2 - mu * t1);
-                if (gq == 0 && !accumulate) { dg_run = (float)dga; db_run = (float)dbe; }
-                else { dg_run = dg_run + (float)dga; db_run = db_run + (float)dbe; }
-            }
-        }
-        __syncthreads();
-    }
-    if (rg == 0 && c < C) { dgamma[c] = dg_run; dbeta[c] = db_run; }
-}
-
+// (the kernels: bn_bwd.h)
 // 8-channel kernels: bf16, no pooling, C / 8 a power of two <= 256 (every layer of the U-Net and of ResNet-50/101);
 // ustrun_debug_flags bit 12 (4096) keeps the 4-channel kernels (A/B runs)
 static bool x8_ok(int C, bool pool, int dtype) {
@@ -1054,6 +455,54 @@ int reduce_blocks(long nwin, int G) {
     if (b > 1024) b = 1024;
     if (b < 1) b = 1;
     return (int)b;
+}
+
+// What the launchers of the three stream passes share: the build that serves a call, and its grid.
+struct BnBwdPlan {
+    bool pool, even, x8;
+    int G, blocks;          // channel groups per block (C / 8 with x8); grid x
+    long nwin;              // windows (pixels, or 2x2 pooling windows) per pass
+    PassOff po;
+};
+
+// pass: BN_REDUCE / BN_APPLY / BN_FROZEN.  sums: the launch leaves partial rows -- the passes' rows share the 1024-row table, so
+// the grid is the reduce pass's; without them it is the apply pass's.
+int bn_bwd_plan(BnBwdPlan& p, int pass, int N, int H, int W, int C, int dtype, int passes, bool has_da, bool has_dp, bool sums,
+                long act_elems, long pool_elems, long aff_stride) {
+    static const char* const names[] = {"bn_bwd_reduce", "bn_bwd_apply", "bn_bwd_frozen"};
+    const char* nm = names[pass];
+    USTRUN_CHECK(dtype_ok(dtype), "%s: dtype %d not built", nm, dtype);
+    USTRUN_CHECK(N > 0 && H > 0 && W > 0 && C % 4 == 0 && C > 0 && passes >= 1 && (!sums || passes <= 64),
+                 "%s: N=%d H=%d W=%d C=%d (must be a multiple of 4) passes=%d", nm, N, H, W, C, passes);
+    p.pool = has_dp;
+    p.even = p.pool && !(H & 1) && !(W & 1);
+    p.x8 = x8_ok(C, p.pool, dtype) && has_da;
+    p.G = p.x8 ? C / 8 : group_size(C / 4);
+    p.nwin = p.pool ? (long)N * ((H + 1) / 2) * ((W + 1) / 2) : (long)N * H * W;
+    USTRUN_CHECK(p.nwin < (1L << 31), "%s: %ld windows per pass", nm, p.nwin);
+    if (sums) {
+        p.blocks = reduce_blocks(p.nwin, p.G);
+        if (p.blocks > 1024 / passes) p.blocks = 1024 / passes;
+    } else {
+        const int PL = 256 / p.G;
+        const long b = (p.nwin + (long)PL * 4 - 1) / ((long)PL * 4);
+        p.blocks = b > 4096 ? 4096 : (int)b;
+    }
+    p.po = {act_elems, pool_elems, aff_stride, sums ? (long)p.blocks * 2 * C : 0, pass == BN_FROZEN ? 0 : 3L * C};
+    note_bn_variant(pass, act_esz(dtype), p.even, p.pool, p.x8);
+    return 0;
+}
+
+// the 4-channel kernels' <POOL, ESZ, EVEN> from (pool, dtype, even): f(std::bool_constant, std::integral_constant<int>, std::bool_constant)
+template <typename F>
+void bn_bwd_dispatch(int dtype, const BnBwdPlan& p, F&& f) {
+    auto by_esz = [&](auto pool, auto even) {
+        if (dtype == USTRUN_D16) f(pool, std::integral_constant<int, 2>{}, even);
+        else f(pool, std::integral_constant<int, 4>{}, even);
+    };
+    if (p.even) by_esz(std::true_type{}, std::true_type{});
+    else if (p.pool) by_esz(std::true_type{}, std::false_type{});
+    else by_esz(std::false_type{}, std::false_type{});
 }
 
 }  // namespace
@@ -1240,39 +689,80 @@ int bn_bwd_reduce_passes(const void* da, const void* dp, const void* y, const fl
                          const float* mean, const float* rstd, const float* gamma, int N, int H, int W, int C, float* dgamma,
                          float* dbeta, int accumulate, float* coef, float* partials, int64_t partials_bytes, int dtype,
                          int passes, long act_elems, long pool_elems, long aff_stride, hipStream_t s) {
-    USTRUN_CHECK(dtype_ok(dtype), "bn_bwd_reduce: dtype %d not built", dtype);
     USTRUN_CHECK((da || dp) && y && scale && shift && mean && rstd && gamma && coef && partials, "bn_bwd_reduce: null pointer");
-    USTRUN_CHECK(C % 4 == 0 && C > 0 && passes >= 1 && passes <= 64, "bn_bwd_reduce: C=%d must be a multiple of 4", C);
     USTRUN_CHECK(partials_bytes >= ustrun_bn_bwd_partials_bytes((int64_t)N * H * W, C), "bn_bwd_reduce: partials too small");
-    const bool pool = dp != nullptr;
-    const bool x8 = x8_ok(C, pool, dtype) && da;
-    const int G = x8 ? C / 8 : group_size(C / 4);
-    const long nwin = pool ? (long)N * ((H + 1) / 2) * ((W + 1) / 2) : (long)N * H * W;
-    USTRUN_CHECK(nwin < (1L << 31), "bn_bwd_reduce: %ld windows per pass", nwin);
-    int blocks = reduce_blocks(nwin, G);
-    if (blocks > 1024 / passes) blocks = 1024 / passes;          // all passes' rows share the 1024-row table
-    const PassOff po = {act_elems, pool_elems, aff_stride, (long)blocks * 2 * C, 3L * C};
-    note_bn_variant(0, act_esz(dtype), pool && !(H & 1) && !(W & 1), pool, x8);
-    if (x8) {
-        hipLaunchKernelGGL(bn_bwd_reduce_x8_kernel, dim3(blocks, passes), dim3(256), 0, s, (const elt_t*)da, (const elt_t*)y, scale, shift,
-                           nwin, C, G, partials, po);
-        USTRUN_LAUNCH_CHECK("bn_bwd_reduce");
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel<false>, dim3(cdiv(C, 32)), dim3(1024), 0, s, partials, blocks, C, (double)N * H * W, gamma,
-                           mean, rstd, dgamma, dbeta, accumulate, coef, passes, po, 2L * C, 0L, 0);
-        USTRUN_LAUNCH_CHECK("bn_bwd_finalize");
-        return 0;
-    }
-#define USTRUN_BN_REDUCE(P, E, V)                                                                                      \
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<P, E, V>), dim3(blocks, passes), dim3(256), 0, s, (const float*)da,      \
-                       (const float*)dp, (const float*)y, scale, shift, N, H, W, C, G, partials, po)
-    const bool even = pool && !(H & 1) && !(W & 1);
-    if (dtype == USTRUN_D16) { if (even) USTRUN_BN_REDUCE(true, 2, true); else if (pool) USTRUN_BN_REDUCE(true, 2, false); else USTRUN_BN_REDUCE(false, 2, false); }
-    else { if (even) USTRUN_BN_REDUCE(true, 4, true); else if (pool) USTRUN_BN_REDUCE(true, 4, false); else USTRUN_BN_REDUCE(false, 4, false); }
-#undef USTRUN_BN_REDUCE
+    BnBwdPlan p;
+    USTRUN_TRY(bn_bwd_plan(p, BN_REDUCE, N, H, W, C, dtype, passes, da != nullptr, dp != nullptr, true, act_elems, pool_elems, aff_stride));
+    const dim3 grid(p.blocks, passes);
+    if (p.x8)
+        hipLaunchKernelGGL(bn_bwd_reduce_x8_kernel, grid, dim3(256), 0, s, (const elt_t*)da, (const elt_t*)y, scale, shift, p.nwin, C, p.G,
+                           partials, p.po);
+    else
+        bn_bwd_dispatch(dtype, p, [&](auto P, auto E, auto V) {
+            hipLaunchKernelGGL((bn_bwd_reduce_kernel<decltype(P)::value, decltype(E)::value, decltype(V)::value>), grid, dim3(256), 0, s,
+                               (const float*)da, (const float*)dp, (const float*)y, scale, shift, N, H, W, C, p.G, partials, p.po);
+        });
     USTRUN_LAUNCH_CHECK("bn_bwd_reduce");
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel<false>, dim3(cdiv(C, 32)), dim3(1024), 0, s, partials, blocks, C, (double)N * H * W, gamma,
-                       mean, rstd, dgamma, dbeta, accumulate, coef, passes, po, 2L * C, 0L, 0);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel<false>, dim3(cdiv(C, 32)), dim3(1024), 0, s, partials, p.blocks, C, (double)N * H * W, gamma,
+                       mean, rstd, dgamma, dbeta, accumulate, coef, passes, p.po, 2L * C, 0L, 0);
     USTRUN_LAUNCH_CHECK("bn_bwd_finalize");
+    return 0;
+}
+
+int bn_bwd_apply_passes(const void* da, const void* dp, const void* y, const float* scale, const float* shift,
+                        const float* coef, int N, int H, int W, int C, void* dy, int dtype, int passes, long act_elems,
+                        long pool_elems, long aff_stride, hipStream_t s) {
+    USTRUN_CHECK((da || dp) && y && scale && shift && coef && dy, "bn_bwd_apply: null pointer");
+    BnBwdPlan p;
+    USTRUN_TRY(bn_bwd_plan(p, BN_APPLY, N, H, W, C, dtype, passes, da != nullptr, dp != nullptr, false, act_elems, pool_elems, aff_stride));
+    const dim3 grid(p.blocks, passes);
+    if (p.x8)
+        hipLaunchKernelGGL(bn_bwd_apply_x8_kernel, grid, dim3(256), 0, s, (const elt_t*)da, (const elt_t*)y, scale, shift, coef, p.nwin, C,
+                           p.G, (elt_t*)dy, p.po);
+    else
+        bn_bwd_dispatch(dtype, p, [&](auto P, auto E, auto V) {
+            hipLaunchKernelGGL((bn_bwd_apply_kernel<decltype(P)::value, decltype(E)::value, decltype(V)::value>), grid, dim3(256), 0, s,
+                               (const float*)da, (const float*)dp, (const float*)y, scale, shift, coef, N, H, W, C, p.G, (float*)dy, p.po);
+        });
+    USTRUN_LAUNCH_CHECK("bn_bwd_apply");
+    return 0;
+}
+
+// Frozen BatchNorm's backward, one launch for all passes (+ the finalize when the parameters want gradients): see
+// bn_bwd_frozen_kernel.  dgamma == nullptr: no rows, no finalize, `partials` untouched.
+int bn_bwd_frozen_passes(const void* da, const void* dp, const void* y, const float* scale, const float* shift, const float* mean,
+                         const float* rstd, int N, int H, int W, int C, void* dy, float* dgamma, float* dbeta, int accumulate,
+                         float* partials, int64_t partials_bytes, int dtype, int passes, long act_elems, long pool_elems,
+                         long aff_stride, hipStream_t s) {
+    USTRUN_CHECK((da || dp) && y && scale && shift && dy, "bn_bwd_frozen: null pointer");
+    const bool sums = dgamma != nullptr;
+    USTRUN_CHECK(sums == (dbeta != nullptr), "bn_bwd_frozen: dgamma and dbeta come together");
+    USTRUN_CHECK(!sums || (mean && rstd && partials), "bn_bwd_frozen: the sums need mean, rstd and the partials scratch");
+    USTRUN_CHECK(!sums || partials_bytes >= ustrun_bn_bwd_partials_bytes((int64_t)N * H * W, C), "bn_bwd_frozen: partials too small");
+    USTRUN_CHECK(!dp || (H >= 2 && W >= 2), "bn_bwd_frozen: pooled windows need H, W >= 2 (%dx%d)", H, W);
+    BnBwdPlan p;
+    USTRUN_TRY(bn_bwd_plan(p, BN_FROZEN, N, H, W, C, dtype, passes, da != nullptr, dp != nullptr, sums, act_elems, pool_elems, aff_stride));
+    const dim3 grid(p.blocks, passes);
+    auto with_sums = [&](auto f) { if (sums) f(std::true_type{}); else f(std::false_type{}); };
+    if (p.x8)
+        with_sums([&](auto S) {
+            hipLaunchKernelGGL(bn_bwd_frozen_x8_kernel<decltype(S)::value>, grid, dim3(256), 0, s, (const elt_t*)da, (const elt_t*)y, scale,
+                               shift, p.nwin, C, p.G, (elt_t*)dy, partials, p.po);
+        });
+    else
+        bn_bwd_dispatch(dtype, p, [&](auto P, auto E, auto V) {
+            with_sums([&](auto S) {
+                hipLaunchKernelGGL((bn_bwd_frozen_kernel<decltype(P)::value, decltype(E)::value, decltype(V)::value, decltype(S)::value>), grid,
+                                   dim3(256), 0, s, (const float*)da, (const float*)dp, (const float*)y, scale, shift, N, H, W, C, p.G,
+                                   (float*)dy, partials, p.po);
+            });
+        });
+    USTRUN_LAUNCH_CHECK("bn_bwd_frozen");
+    if (sums) {         // no coefficient table: dy does not depend on the sums
+        hipLaunchKernelGGL((bn_bwd_finalize_kernel<false, false>), dim3(cdiv(C, 32)), dim3(1024), 0, s, partials, p.blocks, C, 0.0,
+                           (const float*)nullptr, mean, rstd, dgamma, dbeta, accumulate, (float*)nullptr, passes, p.po, 2L * C, 0L, 0);
+        USTRUN_LAUNCH_CHECK("bn_bwd_finalize");
+    }
     return 0;
 }
 
@@ -1305,39 +795,6 @@ int bn_bwd_finalize_stat(float* stat, int rows, int passes, int C, int64_t count
                            rstd, dgamma, dbeta, accumulate, coef, passes, po, 2L * C, 0L, 0);
     }
     USTRUN_LAUNCH_CHECK("bn_bwd_finalize");
-    return 0;
-}
-
-int bn_bwd_apply_passes(const void* da, const void* dp, const void* y, const float* scale, const float* shift,
-                        const float* coef, int N, int H, int W, int C, void* dy, int dtype, int passes, long act_elems,
-                        long pool_elems, long aff_stride, hipStream_t s) {
-    USTRUN_CHECK(dtype_ok(dtype), "bn_bwd_apply: dtype %d not built", dtype);
-    USTRUN_CHECK((da || dp) && y && scale && shift && coef && dy, "bn_bwd_apply: null pointer");
-    USTRUN_CHECK(C % 4 == 0 && C > 0, "bn_bwd_apply: C=%d must be a multiple of 4", C);
-    const bool pool = dp != nullptr;
-    const bool x8 = x8_ok(C, pool, dtype) && da;
-    const int G = x8 ? C / 8 : group_size(C / 4);
-    const long nwin = pool ? (long)N * ((H + 1) / 2) * ((W + 1) / 2) : (long)N * H * W;
-    USTRUN_CHECK(nwin < (1L << 31), "bn_bwd_apply: %ld windows per pass", nwin);
-    const int PL = 256 / G;
-    long blocks = (nwin + (long)PL * 4 - 1) / ((long)PL * 4);
-    if (blocks > 4096) blocks = 4096;
-    const PassOff po = {act_elems, pool_elems, aff_stride, 0, 3L * C};
-    note_bn_variant(1, act_esz(dtype), pool && !(H & 1) && !(W & 1), pool, x8);
-    if (x8) {
-        hipLaunchKernelGGL(bn_bwd_apply_x8_kernel, dim3((int)blocks, passes), dim3(256), 0, s, (const elt_t*)da, (const elt_t*)y, scale, shift,
-                           coef, nwin, C, G, (elt_t*)dy, po);
-        USTRUN_LAUNCH_CHECK("bn_bwd_apply");
-        return 0;
-    }
-#define USTRUN_BN_APPLY(P, E, V)                                                                                            \
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<P, E, V>), dim3((int)blocks, passes), dim3(256), 0, s, (const float*)da,       \
-                       (const float*)dp, (const float*)y, scale, shift, coef, N, H, W, C, G, (float*)dy, po)
-    const bool even = pool && !(H & 1) && !(W & 1);
-    if (dtype == USTRUN_D16) { if (even) USTRUN_BN_APPLY(true, 2, true); else if (pool) USTRUN_BN_APPLY(true, 2, false); else USTRUN_BN_APPLY(false, 2, false); }
-    else { if (even) USTRUN_BN_APPLY(true, 4, true); else if (pool) USTRUN_BN_APPLY(true, 4, false); else USTRUN_BN_APPLY(false, 4, false); }
-#undef USTRUN_BN_APPLY
-    USTRUN_LAUNCH_CHECK("bn_bwd_apply");
     return 0;
 }
 
@@ -1395,67 +852,6 @@ extern "C" int ustrun_bn_bwd_apply(const void* da, const void* dp, const void* y
                                    int dtype, ustrun_stream_t s) {
     return bn_bwd_apply_passes(da, dp, y, scale, shift, coef, N, H, W, C, dy, dtype, 1, 0, 0, 0, (hipStream_t)s);
 }
-
-namespace ustrun {
-// Frozen BatchNorm's backward, one launch for all passes (+ the finalize when the parameters want gradients): see
-// bn_bwd_frozen_kernel.  dgamma == nullptr: no rows, no finalize, `partials` untouched.
-int bn_bwd_frozen_passes(const void* da, const void* dp, const void* y, const float* scale, const float* shift, const float* mean,
-                         const float* rstd, int N, int H, int W, int C, void* dy, float* dgamma, float* dbeta, int accumulate,
-                         float* partials, int64_t partials_bytes, int dtype, int passes, long act_elems, long pool_elems,
-                         long aff_stride, hipStream_t s) {
-    USTRUN_CHECK(dtype_ok(dtype), "bn_bwd_frozen: dtype %d not built", dtype);
-    USTRUN_CHECK((da || dp) && y && scale && shift && dy, "bn_bwd_frozen: null pointer");
-    USTRUN_CHECK(N > 0 && H > 0 && W > 0 && C % 4 == 0 && C > 0 && passes >= 1 && passes <= 64,
-                 "bn_bwd_frozen: N=%d H=%d W=%d C=%d (a multiple of 4) passes=%d", N, H, W, C, passes);
-    const bool sums = dgamma != nullptr;
-    USTRUN_CHECK(sums == (dbeta != nullptr), "bn_bwd_frozen: dgamma and dbeta come together");
-    USTRUN_CHECK(!sums || (mean && rstd && partials), "bn_bwd_frozen: the sums need mean, rstd and the partials scratch");
-    USTRUN_CHECK(!sums || partials_bytes >= ustrun_bn_bwd_partials_bytes((int64_t)N * H * W, C), "bn_bwd_frozen: partials too small");
-    const bool pool = dp != nullptr;
-    USTRUN_CHECK(!pool || (H >= 2 && W >= 2), "bn_bwd_frozen: pooled windows need H, W >= 2 (%dx%d)", H, W);
-    const bool x8 = x8_ok(C, pool, dtype) && da;
-    const int G = x8 ? C / 8 : group_size(C / 4);
-    const long nwin = pool ? (long)N * ((H + 1) / 2) * ((W + 1) / 2) : (long)N * H * W;
-    USTRUN_CHECK(nwin < (1L << 31), "bn_bwd_frozen: %ld windows per pass", nwin);
-    const int PL = 256 / G;
-    long blocks;
-    if (sums) {             // the passes' rows share the 1024-row table, as bn_bwd_reduce's do
-        blocks = reduce_blocks(nwin, G);
-        if (blocks > 1024 / passes) blocks = 1024 / passes;
-    } else {                // a pure apply pass: bn_bwd_apply's grid
-        blocks = (nwin + (long)PL * 4 - 1) / ((long)PL * 4);
-        if (blocks > 4096) blocks = 4096;
-    }
-    const PassOff po = {act_elems, pool_elems, aff_stride, blocks * 2 * C, 0};
-    const bool even = pool && !(H & 1) && !(W & 1);
-    note_bn_variant(2, act_esz(dtype), even, pool, x8);
-    const dim3 grid((int)blocks, passes);
-    if (x8) {
-        if (sums) hipLaunchKernelGGL(bn_bwd_frozen_x8_kernel<true>, grid, dim3(256), 0, s, (const elt_t*)da, (const elt_t*)y, scale,
-                                     shift, nwin, C, G, (elt_t*)dy, partials, po);
-        else hipLaunchKernelGGL(bn_bwd_frozen_x8_kernel<false>, grid, dim3(256), 0, s, (const elt_t*)da, (const elt_t*)y, scale, shift,
-                                nwin, C, G, (elt_t*)dy, partials, po);
-    } else {
-#define USTRUN_BN_FROZEN(P, E, V)                                                                                                   \
-    do {                                                                                                                            \
-        if (sums) hipLaunchKernelGGL((bn_bwd_frozen_kernel<P, E, V, true>), grid, dim3(256), 0, s, (const float*)da, (const float*)dp, \
-                                     (const float*)y, scale, shift, N, H, W, C, G, (float*)dy, partials, po);                       \
-        else hipLaunchKernelGGL((bn_bwd_frozen_kernel<P, E, V, false>), grid, dim3(256), 0, s, (const float*)da, (const float*)dp,  \
-                                (const float*)y, scale, shift, N, H, W, C, G, (float*)dy, partials, po);                            \
-    } while (0)
-        if (dtype == USTRUN_D16) { if (even) USTRUN_BN_FROZEN(true, 2, true); else if (pool) USTRUN_BN_FROZEN(true, 2, false); else USTRUN_BN_FROZEN(false, 2, false); }
-        else { if (even) USTRUN_BN_FROZEN(true, 4, true); else if (pool) USTRUN_BN_FROZEN(true, 4, false); else USTRUN_BN_FROZEN(false, 4, false); }
-#undef USTRUN_BN_FROZEN
-    }
-    USTRUN_LAUNCH_CHECK("bn_bwd_frozen");
-    if (sums) {
-        hipLaunchKernelGGL(bn_bwd_frozen_finalize_kernel, dim3(cdiv(C, 32)), dim3(1024), 0, s, partials, (int)blocks, C, mean, rstd,
-                           dgamma, dbeta, accumulate, passes, po);
-        USTRUN_LAUNCH_CHECK("bn_bwd_frozen_finalize");
-    }
-    return 0;
-}
-}  // namespace ustrun
 
 extern "C" int ustrun_bn_bwd_frozen(const void* da, const void* dp, const void* y, const float* scale, const float* shift,
                                     const float* mean, const float* rstd, int N, int H, int W, int C, void* dy, float* dgamma,
