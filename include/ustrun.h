@@ -155,7 +155,8 @@ int ustrun_head_bwd(const float* dlogits, const void* y, const float* scale, con
 /* ---- BatchNorm+ReLU (+MaxPool) backward: autograd of unet_parts.py:17-18,34 ------------------
  * Inputs: da (grad wrt the activated output, may be NULL), dp (grad wrt the 2x2-pooled
  * activated output, may be NULL; routed to the window arg-max recomputed from y), y and the
- * forward scale/shift/mean/rstd.  Pass 1 (reduce) produces dgamma/dbeta and the coefficient
+ * forward scale/shift/mean/rstd.  A dp with H < 2 or W < 2 (a pooled map without elements) is
+ * refused by every pass, as ustrun_bn_bwd_frozen refuses it.  Pass 1 (reduce) produces dgamma/dbeta and the coefficient
  * table coef[3][C]; pass 2 (apply) writes dy = coef0*dz + coef1*y + coef2, dz = da_total*(a>0). */
 int64_t ustrun_bn_bwd_partials_bytes(int64_t npix, int C);
 int ustrun_bn_bwd_reduce(const void* da, const void* dp, const void* y, const float* scale,

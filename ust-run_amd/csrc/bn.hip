@@ -474,6 +474,8 @@ int bn_bwd_plan(BnBwdPlan& p, int pass, int N, int H, int W, int C, int dtype, i
     USTRUN_CHECK(dtype_ok(dtype), "%s: dtype %d not built", nm, dtype);
     USTRUN_CHECK(N > 0 && H > 0 && W > 0 && C % 4 == 0 && C > 0 && passes >= 1 && (!sums || passes <= 64),
                  "%s: N=%d H=%d W=%d C=%d (must be a multiple of 4) passes=%d", nm, N, H, W, C, passes);
+    // (H < 2 or W < 2: the pooled map has no elements, and window_dz loads dp[c] whether or not the window has a pooled cell)
+    USTRUN_CHECK(!has_dp || (H >= 2 && W >= 2), "%s: pooled windows need H, W >= 2 (%dx%d)", nm, H, W);
     p.pool = has_dp;
     p.even = p.pool && !(H & 1) && !(W & 1);
     p.x8 = x8_ok(C, p.pool, dtype) && has_da;
