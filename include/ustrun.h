@@ -460,6 +460,42 @@ int ustrun_post_process(const void* pred, int pred_is_i64, int N, int K, int by_
                         int fill_holes, int share_num, int share_den,
                         void* work, int64_t work_bytes, float* out, ustrun_stream_t s);
 
+/* ---- signed distance maps of label planes: the reference's utils/util.py:208-239 (compute_sdf, two
+ * scipy.ndimage.distance_transform_edt calls per image on the host) and the transform utils/metrics.py:52-70
+ * (distance_transform) means to be, on the device for all N * K planes of a batch (csrc/distmap.hip).
+ *
+ * ustrun_signed_dist2: mask as ustrun_surface_metrics reads pred: f32 planes [N,K,H,W] binarised as (x != 0) (by_class = 0), or
+ * a class map [N,H,W], int64 or f32, whose plane c is (x == c + 1) (by_class = 1).  s2[N*K][H][W], one int32 per pixel, is the
+ * SIGNED SQUARED Euclidean distance, exact in integers:
+ *   + d2 to the nearest foreground pixel at a background pixel,   - d2 to the nearest background pixel at a foreground pixel,
+ * over the pixels of the image only -- nothing outside the image is of either kind (scipy's convention, util.py:226-227; NOT the
+ * background-outside convention of ustrun_surface_metrics).  In a plane without the opposite kind (empty or full) every pixel
+ * gets + USTRUN_DIST_NONE resp. - USTRUN_DIST_NONE.  flags[N*K]: 0 = empty plane, 1 = mixed, 2 = full.
+ * H, W in 1..1024 (d2 <= 2 * 1023^2 < 2^21) and N * K <= 32767, else an error before any launch.  work: 16-byte aligned,
+ * ustrun_signed_dist2_work_bytes (-1 + error for sizes out of range), owned by the caller.  Planes are independent, no block
+ * waits for another, no atomics: equal bits on every run.
+ *
+ * ustrun_sdf_from_dist2: the normalisation of util.py:231-234 per plane, from s2 and flags as written above.  With
+ *   pos = d2 of a foreground pixel (0 on background), neg = d2 of a background pixel (0 on foreground),
+ *   maxpos / maxneg = their integer maxima over the plane,
+ *   sdf = sqrt(neg) / sqrt(maxneg) - sqrt(pos) / sqrt(maxpos)      (f32 out; each pixel in f64, rounded once)
+ * -- the reference's (x - min) / (max - min) with both minima 0, which they are on every mixed plane (posdis is 0 on the
+ * background, negdis on the foreground, and both kinds exist).  The inner boundary of util.py:228,234
+ * (find_boundaries(posmask, mode="inner"): a foreground pixel with a background 4-neighbour inside the image, i.e. s2 == -1)
+ * is written as exactly 0.0f.  Planes of flag 0 are all zeros (util.py:224 skips them); planes of flag 2 are all zeros too --
+ * the reference divides 0 / 0 there -- and the flag is how the caller learns of it.  The deepest pixels of a mixed plane are
+ * exactly -1 and +1.  work: 16-byte aligned, ustrun_sdf_from_dist2_work_bytes (the two maxima per plane, found with integer
+ * atomicMax: exact and order-free).
+ * Both entries: asynchronous on s, nothing is allocated, nothing waits for the device; null pointers, sizes out of range and a
+ * short work buffer are refused before any launch.                                                                          */
+#define USTRUN_DIST_NONE 0x7fffffff
+int64_t ustrun_signed_dist2_work_bytes(int N, int K, int H, int W);
+int ustrun_signed_dist2(const void* mask, int mask_is_i64, int N, int K, int by_class, int H, int W,
+                        void* work, int64_t work_bytes, int32_t* s2, int32_t* flags, ustrun_stream_t s);
+int64_t ustrun_sdf_from_dist2_work_bytes(int N, int K, int H, int W);
+int ustrun_sdf_from_dist2(const int32_t* s2, const int32_t* flags, int N, int K, int H, int W,
+                          void* work, int64_t work_bytes, float* sdf, ustrun_stream_t s);
+
 /* ---- SGD(momentum, weight decay) + EMA teacher over flat buffers: train.py:512,848,87-93 ------
  * g += wd*p; v = first ? g : mu*v + g; p -= lr*v; t = alpha*t + (1-alpha)*p                    */
 /* ---- dynamic loss scale of the IEEE-half path: torch.cuda.amp.GradScaler as train.py:552,842-845 uses it, on the device.

@@ -8,7 +8,7 @@
 //
 // Four launches over all N x K planes, both sides (0: prediction, 1: ground truth) in each:
 //   1 border_kernel   col[plane][side][y][x] = 0 on a border pixel, COL_INF elsewhere (u16)
-//   2 colscan_kernel  in place: distance along the column to the nearest border pixel of that side, capped at COL_INF
+//   2 colscan_kernel  (edt_scan.h, shared with distmap.hip) in place: distance along the column to the nearest border pixel of that side, capped at COL_INF
 //   3 rowmin_kernel   one wave per row: at every border pixel x of one side, d2 = min over x' of col_other[x']^2 + (x-x')^2,
 //                     searched outwards from x until (x-x')^2 can no longer win (exact: the candidates left out are >= the minimum);
 //                     the values are appended to that side's list (integer wave-aggregated counter: the order in the list is
@@ -18,12 +18,11 @@
 // The f64 sum is a fixed tree (lane's pixels in x order, xor butterfly, rows in y order, butterfly, waves in order): no
 // floating-point atomics, two runs give the same bits.
 #include "common.h"
+#include "edt_scan.h"        // COL_INF, SURF_MAX, fg_at, colscan_kernel
 
 namespace ustrun {
 namespace {
 
-constexpr int COL_INF = 4096;            // > any distance inside a 1024-pixel column; COL_INF^2 + 1023^2 fits an int
-constexpr int SURF_MAX = 1024;           // H, W limit: d2 <= 2 * 1023^2 < 2^21
 constexpr int L1_BITS = 11, L2_BITS = 10;
 constexpr int ROWS_PER_BLOCK = 4;        // rowmin_kernel: one wave per row
 
@@ -50,15 +49,6 @@ SurfWork surf_carve(void* work, int64_t NK, int64_t H, int64_t W) {
     return w;
 }
 
-// the boolean plane of ustrun_dice_counts: (x == c + 1) of a class map, or (x != 0)
-__device__ __forceinline__ bool fg_at(const void* m, int is64, int by_class, long base, int c, long e) {
-    if (by_class) {
-        const long long v = is64 ? ((const long long*)m)[base + e] : (long long)((const float*)m)[base + e];
-        return v == c + 1;
-    }
-    return is64 ? ((const long long*)m)[base + e] != 0 : ((const float*)m)[base + e] != 0.f;
-}
-
 __device__ __forceinline__ bool border_at(const void* m, int is64, int by_class, long base, int c, int y, int x, int H, int W) {
     const long e = (long)y * W + x;
     if (!fg_at(m, is64, by_class, base, c, e)) return false;
@@ -78,35 +68,6 @@ __global__ __launch_bounds__(256) void border_kernel(const void* pred, const voi
     unsigned short* o = col + (long)plane * 2 * HW;
     o[e] = border_at(pred, pi64, by_class, base, c, y, x, H, W) ? 0 : COL_INF;
     o[HW + e] = border_at(gt, gi64, by_class, base, c, y, x, H, W) ? 0 : COL_INF;
-}
-
-// grid (ceil(W / 64), N * K * 2), one thread per column: down, then up, 8 rows loaded ahead of the dependent chain
-__global__ __launch_bounds__(64) void colscan_kernel(int H, int W, unsigned short* __restrict__ col) {
-    const int x = blockIdx.x * 64 + threadIdx.x;
-    if (x >= W) return;
-    unsigned short* p = col + (long)blockIdx.y * H * W + x;
-    int d = COL_INF;
-    for (int y0 = 0; y0 < H; y0 += 8) {
-        int v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = y0 + j < H ? p[(long)(y0 + j) * W] : COL_INF;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            d = v[j] == 0 ? 0 : min(d + 1, COL_INF);
-            if (y0 + j < H) p[(long)(y0 + j) * W] = (unsigned short)d;
-        }
-    }
-    d = COL_INF;
-    for (int y0 = H - 1; y0 >= 0; y0 -= 8) {
-        int v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = y0 - j >= 0 ? p[(long)(y0 - j) * W] : COL_INF;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            d = min(v[j], min(d + 1, COL_INF));
-            if (y0 - j >= 0) p[(long)(y0 - j) * W] = (unsigned short)d;
-        }
-    }
 }
 
 __device__ __forceinline__ double wave_sum_f64(double v) {

@@ -624,6 +624,69 @@ def post_process(pred, by_class=False, n_classes=1, fill_holes=True, min_share=(
     return out
 
 
+DIST_NONE = 0x7fffffff          # USTRUN_DIST_NONE: |s2| of a pixel whose plane has no pixel of the opposite kind
+PLANE_EMPTY, PLANE_MIXED, PLANE_FULL = 0, 1, 2
+
+
+def _dist_planes(mask, by_class, num_classes, who):
+    if not torch.is_tensor(mask) or not mask.is_cuda or mask.dtype not in (torch.float32, torch.int64):
+        raise RuntimeError(f"{who}: mask must be a float32 or int64 HIP tensor, got "
+                           f"{getattr(mask, 'dtype', type(mask))} on {getattr(mask, 'device', 'the host')}")
+    if by_class:
+        if mask.dim() != 3 or num_classes is None or int(num_classes) < 1:
+            raise RuntimeError(f"{who}: by_class takes a class map [N,H,W] and num_classes >= 1, got {tuple(mask.shape)}, {num_classes}")
+        K = int(num_classes)
+    else:
+        if mask.dim() not in (3, 4) or mask.dtype != torch.float32:
+            raise RuntimeError(f"{who}: mask must be float32 planes [N,(K,)H,W] (or a class map with by_class), got "
+                               f"{mask.dtype} {tuple(mask.shape)}")
+        K = mask.shape[1] if mask.dim() == 4 else 1
+        if num_classes is not None and int(num_classes) != K:
+            raise RuntimeError(f"{who}: num_classes {num_classes} against {K} planes")
+    return mask.contiguous(), mask.shape[0], K, mask.shape[-2], mask.shape[-1]
+
+
+@torch.no_grad()
+def signed_dist2(mask, by_class=False, num_classes=None):
+    """Exact signed squared Euclidean distances of every plane of `mask` (ustrun_signed_dist2; taken as `surface_metrics` takes
+    pred: float32 planes [N,(K,)H,W] binarised as != 0, or with by_class an int64 / float32 class map [N,H,W] whose plane c is
+    == c + 1) -> (s2 int32 [N,K,H,W], flags int32 [N,K]) on the device: + d2 to the nearest foreground pixel at a background
+    pixel, - d2 to the nearest background pixel at a foreground pixel, inside the image only (scipy's convention);
+    flags 0 / 1 / 2 = empty / mixed / full plane, whose pixels hold +- DIST_NONE where no opposite kind exists.  Integer
+    labels, no gradient; nothing waits for the device."""
+    lib = L.lib()
+    mask, N, K, H, W = _dist_planes(mask, by_class, num_classes, "signed_dist2")
+    nb = lib.ustrun_signed_dist2_work_bytes(N, K, H, W)
+    if nb < 0:
+        L.check(1, "ustrun_signed_dist2_work_bytes")
+    work = torch.empty(nb, dtype=torch.uint8, device=mask.device)
+    s2 = torch.empty((N, K, H, W), dtype=torch.int32, device=mask.device)
+    flags = torch.empty((N, K), dtype=torch.int32, device=mask.device)
+    L.check(lib.ustrun_signed_dist2(mask.data_ptr(), int(mask.dtype == torch.int64), N, K, int(bool(by_class)), H, W,
+                                    work.data_ptr(), nb, s2.data_ptr(), flags.data_ptr(), stream_ptr()), "ustrun_signed_dist2")
+    return s2, flags
+
+
+@torch.no_grad()
+def signed_distance_map(mask, by_class=False, num_classes=None):
+    """The normalised signed distance map of the reference's compute_sdf (utils/util.py:208-239) for every plane of `mask`
+    (as `signed_dist2` takes it) -> (sdf float32 [N,K,H,W], flags int32 [N,K]) on the device: in [-1, 0) inside, exactly 0 on
+    the inner boundary, in (0, 1] outside, -1 and +1 at the deepest pixels.  Empty planes (flag 0) are zeros as in the
+    reference; full planes (flag 2), where the reference divides 0 / 0, are zeros too -- read the flags.  A ground-truth
+    target: not differentiable; nothing waits for the device."""
+    lib = L.lib()
+    s2, flags = signed_dist2(mask, by_class, num_classes)
+    N, K, H, W = s2.shape
+    nb = lib.ustrun_sdf_from_dist2_work_bytes(N, K, H, W)
+    if nb < 0:
+        L.check(1, "ustrun_sdf_from_dist2_work_bytes")
+    work = torch.empty(nb, dtype=torch.uint8, device=s2.device)
+    sdf = torch.empty((N, K, H, W), dtype=torch.float32, device=s2.device)
+    L.check(lib.ustrun_sdf_from_dist2(s2.data_ptr(), flags.data_ptr(), N, K, H, W, work.data_ptr(), nb, sdf.data_ptr(),
+                                      stream_ptr()), "ustrun_sdf_from_dist2")
+    return sdf, flags
+
+
 def sgd_ema(p, g, v, t, lr, momentum, weight_decay, first, alpha, grad_scale=1.0):
     """Fused SGD(momentum, wd) step on flat f32 buffers + EMA teacher update (train.py:512,848,87-93)."""
     lib = L.lib()

@@ -9,6 +9,8 @@ whole masks to the host.
 (binary.dc / jc / hd95 / asd, train.py:306-325): the device (ustrun.functional.surface_metrics) delivers, per sample and
 part, the border sizes, the two integer order statistics of the squared surface distances and the sum of the
 prediction's distances; the square roots, numpy's linear percentile and the reference's empty-mask rules are applied here.
+
+`distance_transform` is the Euclidean distance transform utils/metrics.py:52-70 means to be, computed on the device.
 """
 import numpy as np
 
@@ -66,6 +68,28 @@ def surface_from_records(records, counts, where=""):
     asd = total / np.maximum(nbp, 1)
     empty = s == 0
     return dc, jc, np.where(empty, EMPTY_PRED_VALUE, hd), np.where(empty, EMPTY_PRED_VALUE, asd)
+
+
+def distance_transform(bitmap):
+    """Euclidean distance from every pixel of bitmap [B,H,W] to the nearest true pixel of its plane (0 on true pixels, inf over
+    a plane without one), from the exact integer squared distances of ustrun.functional.signed_dist2.
+      numpy in -> float64 out, the square root taken in float64 of the exact integer;  HIP tensor in -> float32 HIP tensor out.
+    This is deliberately the exact transform and NOT what the reference's function of this name returns: its square root
+    (utils/metrics.py:69) sits inside the column loop, so the whole plane is rooted once per column and every finite value
+    ends at 1.0 -- on a 2 x 24 x 40 batch its result is off the true transform by up to 19 pixels."""
+    import torch
+    from ustrun import functional as F
+    if len(bitmap.shape) != 3:
+        raise ValueError(f"distance_transform: bitmap must be [B,H,W], got {tuple(bitmap.shape)}")
+    if torch.is_tensor(bitmap):
+        if not bitmap.is_cuda:
+            raise TypeError("distance_transform: a tensor must live on the device (pass a numpy array for host data)")
+        s2, _ = F.signed_dist2((bitmap != 0).float())
+        d = s2[:, 0].clamp_min(0).double().sqrt().float()        # d2 < 2^21: rounding the f64 root once is the correctly rounded f32 root
+        return torch.where(s2[:, 0] == F.DIST_NONE, torch.full_like(d, float("inf")), d)
+    s2, _ = F.signed_dist2(torch.from_numpy((np.asarray(bitmap) != 0).astype(np.float32)).cuda())
+    s2 = s2.cpu().numpy()[:, 0]
+    return np.where(s2 == F.DIST_NONE, np.inf, np.sqrt(np.maximum(s2, 0).astype(np.float64)))
 
 
 def dice_coefficient_numpy(binary_segmentation, binary_gt_label):

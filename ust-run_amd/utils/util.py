@@ -1,9 +1,11 @@
 """Checkpoint I/O and meters used by the training scripts -- surface of the reference's
-utils/util.py:167-183,259-297 -- and the two overlay pictures of utils/util.py:346-390 that test.py --save_img
-writes (the rest of that file is dead code there).  state_dict keys are identical to the reference's, so
+utils/util.py:167-183,259-297 --, the two overlay pictures of utils/util.py:346-390 that test.py --save_img
+writes, and compute_sdf of utils/util.py:208-239, the signed distance map shape-aware losses regress on, computed on
+the device (the rest of that file is dead code there).  state_dict keys are identical to the reference's, so
 checkpoints interchange in both directions."""
 import os
 
+import numpy as np
 import torch
 
 
@@ -73,3 +75,46 @@ def draw_mask_and_save(img, pred, save_path='./img/1/example.png'):
     from ustrun import render
     img, pred = _one_image(img, pred)
     _write(render.render_mask(img, pred), save_path)
+
+
+def _sdf_planes(in_shape, out_shape):
+    """compute_sdf's shapes, checked before anything touches the device -> (B, H, W)"""
+    in_shape, out_shape = tuple(int(d) for d in in_shape), tuple(int(d) for d in out_shape)
+    if len(in_shape) > 3 or len(out_shape) > 4 or (len(out_shape) == 4 and out_shape[1] != 1):
+        raise NotImplementedError(f"compute_sdf: only 2-D planes are built -- img_gt [B,H,W] with out_shape [B,H,W] or "
+                                  f"[B,1,H,W]; 3-D volumes such as img_gt {in_shape} / out_shape {out_shape} are not")
+    if len(in_shape) != 3 or out_shape not in (in_shape, (in_shape[0], 1) + in_shape[1:]):
+        raise ValueError(f"compute_sdf: img_gt {in_shape} must be [B,H,W] and out_shape {out_shape} the same or [B,1,H,W]")
+    return in_shape
+
+
+def compute_sdf(img_gt, out_shape):
+    """utils/util.py:208-239 on the device (ustrun.functional.signed_distance_map): the signed distance map of every binary
+    mask img_gt[b] (binarised as != 0), normalised to [-1, 1] -- negative inside, 0 on the inner boundary, positive outside;
+    all zeros for an empty mask, as the reference leaves it.
+      numpy [B,H,W] (any integer or bool dtype) -> float64 ndarray of out_shape: the exact integer squared distances come from
+        the device, square roots and quotients are taken in float64 as the reference takes them.  A mask with no background,
+        where the reference divides 0 / 0, raises ValueError naming the sample (the call waits for the device anyway).
+      HIP tensor [B,H,W] -> float32 HIP tensor of out_shape, no host trip and no wait; a full mask gives zeros there --
+        ustrun.functional.signed_distance_map returns the per-plane flags that tell.
+    out_shape is [B,H,W] or [B,1,H,W]; the reference's 3-D volumes are not built (NotImplementedError)."""
+    B, H, W = _sdf_planes(img_gt.shape, out_shape)
+    from ustrun import functional as F
+    if torch.is_tensor(img_gt):
+        if not img_gt.is_cuda:
+            raise TypeError("compute_sdf: a tensor must live on the device (pass a numpy array for host data)")
+        sdf, _ = F.signed_distance_map((img_gt != 0).float())
+        return sdf.reshape(tuple(out_shape))
+    mask = np.asarray(img_gt) != 0
+    s2, flags = F.signed_dist2(torch.from_numpy(mask.astype(np.float32)).cuda())
+    s2, flags = s2.cpu().numpy()[:, 0].astype(np.int64), flags.cpu().numpy()[:, 0]
+    if (flags == F.PLANE_FULL).any():
+        b = int(np.argmax(flags == F.PLANE_FULL))
+        raise ValueError(f"compute_sdf: sample {b} has no background pixel: its signed distance map is undefined "
+                         "(the reference divides 0 / 0 here)")
+    out = np.zeros((B, H, W), np.float64)
+    for b in np.flatnonzero(flags == F.PLANE_MIXED):
+        pos, neg = np.sqrt(np.maximum(-s2[b], 0).astype(np.float64)), np.sqrt(np.maximum(s2[b], 0).astype(np.float64))
+        out[b] = neg / neg.max() - pos / pos.max()
+        out[b][s2[b] == -1] = 0.0
+    return out.reshape(tuple(out_shape))
