@@ -316,6 +316,71 @@ def test_conv3x3_f32x3(n, c0, c1, co, h, w, exact):
             lib.ustrun_debug_flags(old)
 
 
+@pytest.mark.parametrize("n,gn,ci,co,h,w", [
+    (4, 1, 64, 64, 8, 16),          # the all-taps weight-gradient plan: blocks of 4 tiles = 2 images, the constants change inside a block's walk
+    (4, 2, 128, 128, 8, 16),        # the change falls on a block boundary; the forward runs its 128-column build
+    (3, 1, 64, 64, 9, 21),          # 18 ragged tiles in blocks of 5: image boundaries mid-block at tiles 6 and 12, with the edge masks
+])
+def test_conv3x3_f32x3_batched_passes(n, gn, ci, co, h, w):
+    """Forward and weight gradient under dtype 3 over batched passes (gN images per pass, BatchNorm constants per pass, ReLU on
+    load) against torch in float64 on test_conv3x3_f32x3's exact data: every product and sum is a multiple of 0.5 far below 2^24,
+    so the reference is exactly representable and the exact-case bound holds by exact arithmetic alone.  One batched launch
+    (ustrun_debug_flags2 = 0) and one launch per pass (bit 1) must agree bit for bit; dw sits between sentinel zones."""
+    l = L()
+    lib = l.lib()
+    G = n // gn
+    g = torch.Generator().manual_seed(ci + co + h + n)
+    ri = lambda lo, hi, *s: torch.randint(lo, hi + 1, s, generator=g).float()
+    y0 = ri(-3, 3, n, ci, h, w)
+    sc = torch.tensor([0.5, 1.0, 2.0, -1.0])[torch.randint(0, 4, (G, ci), generator=g)]
+    sh = ri(-1, 1, G, ci)
+    a = torch.relu(y0 * sc.repeat_interleave(gn, 0)[:, :, None, None] + sh.repeat_interleave(gn, 0)[:, :, None, None])
+    wt, dy = ri(-3, 3, co, ci, 3, 3), ri(-3, 3, n, co, h, w)
+    wr = wt.double().requires_grad_(True)
+    y64 = F.conv2d(a.double(), wr, None, 1, 1)
+    y64.backward(dy.double())
+    y64, dw64 = y64.detach(), wr.grad
+    assert float(y64.abs().max()) < 2 ** 24 and float(dw64.abs().max()) < 2 ** 24
+    aff = torch.zeros(G, 4, ci)
+    aff[:, 0], aff[:, 1] = sc, sh
+    affg, y0g, dyg = aff.cuda(), nhwc(y0), nhwc(dy)
+    src = l.nhwc_src(y0g.data_ptr(), ci, h, w, affg.data_ptr(), affg.data_ptr() + 4 * ci, relu=1, gN=gn, gstride=4 * ci)
+    sarr = (l.Src * 1)(src)
+    wf, _ = pack_conv_x3(wt)
+    nb = lib.ustrun_wgrad_partials_bytes(9, ci, co, n * h * w)
+    Z, slab = 512, 9 * ci * co
+    assert nb // 4 >= 2 * slab
+    stat = torch.zeros(lib.ustrun_conv_mtiles(n, h, w, co), 2, co, device="cuda")
+    got = []
+    for flags2 in (0, 2):           # one batched launch; one launch per pass
+        old = lib.ustrun_debug_flags2(flags2)
+        try:
+            y = torch.empty(n, h, w, co, device="cuda")
+            # which path ran: statistics rows without a row count are served by the single batched launch only, and only the
+            # batched weight gradient splits its tiles over more than one slab (a pass alone has at most 6 tiles: one block)
+            rc = lib.ustrun_conv3x3_fwd(sarr, 1, wf.data_ptr(), n, h, w, co, y.data_ptr(), stat.data_ptr(), 3, None)
+            if flags2 == 0:
+                l.check(rc, "fwd")
+            else:
+                assert rc != 0 and b"batched passes need" in lib.ustrun_last_error(), "the forward did not go pass by pass"
+                l.check(lib.ustrun_conv3x3_fwd(sarr, 1, wf.data_ptr(), n, h, w, co, y.data_ptr(), None, 3, None), "fwd")
+            buf = torch.full((Z + co * ci * 9 + Z,), 9.0, device="cuda")
+            dw = buf[Z:Z + co * ci * 9].view(co, ci, 3, 3)
+            part = torch.full((nb // 4,), 5.0, device="cuda")
+            l.check(lib.ustrun_conv3x3_wgrad(sarr, 1, dyg.data_ptr(), n, h, w, co, dw.data_ptr(), 0, part.data_ptr(), nb, 3, None), "wgrad")
+            assert bool((part[slab:2 * slab] == 5.0).all()) == (flags2 != 0), "weight gradient: not the path this flag selects"
+        finally:
+            lib.ustrun_debug_flags2(old)
+        ry, rw = rel(from_nhwc(y), y64), rel(dw.cpu(), dw64)
+        print(f"flags2 {flags2}: fwd rel {ry:.3e}, wgrad rel {rw:.3e}")
+        assert ry < 1e-7, (flags2, ry)
+        assert rw < 1e-7, (flags2, rw)
+        assert bool((buf[:Z] == 9.0).all()) and bool((buf[-Z:] == 9.0).all()), "weight gradient wrote outside dw"
+        got.append((y.cpu(), dw.cpu().clone()))
+    assert torch.equal(got[0][0], got[1][0]), "forward: batched launch and per-pass launches differ"
+    assert torch.equal(got[0][1], got[1][1]), "weight gradient: batched launch and per-pass launches differ"
+
+
 @pytest.mark.parametrize("n,c,h,w", [(2, 3, 16, 32), (1, 1, 19, 37), (3, 3, 40, 33), (4, 3, 136, 96), (8, 3, 256, 256), (1, 2, 3, 17), (2, 3, 5, 48)])
 def test_conv_first_weight_gradient_f32x3(n, c, h, w):
     """The first convolution's weight gradient under dtype 3 (f32 dY): the streaming kernel with three-term products against

@@ -412,10 +412,7 @@ struct WgOpX3 : WgPieces<256, 3> {                       // dtype USTRUN_F32X3: 
     static constexpr const char* NAME = "conv_first_wgrad_x3";
     static __device__ __forceinline__ void stage(char* sl, int lane, const u32x4 (&d)[NP], const unsigned (&m)[NP]) {
 #pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            char* dst = sl + lds_off(i, lane);
-            split4(__builtin_bit_cast(f32x4, and4(d[i], m[i])), *(u32x2*)dst, *(u32x2*)(dst + FTW * WRB), *(u32x2*)(dst + 2 * FTW * WRB));
-        }
+        for (int i = 0; i < NP; ++i) store_planes(split3(__builtin_bit_cast(f32x4, and4(d[i], m[i]))), sl + lds_off(i, lane), FTW * WRB);
     }
     static __device__ __forceinline__ afrag a_frag(const float (&v)[8]) {
         u32x2 lo[3], hi[3];

@@ -233,7 +233,7 @@ extern "C" int ustrun_conv3x3_fwd_rows(const ustrun_src_t* srcs, int nsrc, const
     USTRUN_CHECK(G >= 1, "conv3x3_fwd: inconsistent pass groups");
     a.pass_gN = gN;
     // one launch per pass -- unless the kernel picks the pass's constants per image (the 16-bit halo kernel, the halo-tiled x3 kernel)
-    if (G > 1 && !(dtype == USTRUN_D16 && halo_supported(a)) && !(dtype == USTRUN_F32X3 && !first && conv3x3_x3_supported(a) && !(g_debug_flags2 & 2))) {      // (ustrun_debug_flags2 bit 1: x3 per pass, A/B runs)
+    if (G > 1 && !(dtype == USTRUN_D16 && halo_supported(a)) && !(dtype == USTRUN_F32X3 && !first && conv3x3_x3_supported(a) && !(g_debug_flags2 & X3_DBG2_PER_PASS))) {      // (ustrun_debug_flags2 bit 1: x3 per pass, A/B runs)
         USTRUN_CHECK(!stat || stat_rows, "conv3x3_fwd: batched passes need ustrun_conv3x3_fwd_rows");
         int total = 0;
         for (int g = 0; g < G; ++g) {
@@ -455,7 +455,7 @@ extern "C" int ustrun_conv3x3_wgrad(const ustrun_src_t* srcs, int nsrc, const vo
         int gN = 0;
         const int G = src_groups(srcs, nsrc, N, &gN);
         USTRUN_CHECK(G >= 1, "conv3x3_wgrad: inconsistent pass groups");
-        if (G > 1 && !(dtype == USTRUN_D16 && wgrad_halo_supported(a)) && !(dtype == USTRUN_F32X3 && wgrad_x3_supported(a) && !(g_debug_flags2 & 2))) {
+        if (G > 1 && !(dtype == USTRUN_D16 && wgrad_halo_supported(a)) && !(dtype == USTRUN_F32X3 && wgrad_x3_supported(a) && !(g_debug_flags2 & X3_DBG2_PER_PASS))) {
             for (int g = 0; g < G; ++g) {
                 ustrun_src_t sl[2];
                 for (int i = 0; i < nsrc; ++i) sl[i] = src_slice(srcs[i], g, gN, dtype);
@@ -481,7 +481,7 @@ extern "C" int ustrun_conv3x3_wgrad(const ustrun_src_t* srcs, int nsrc, const vo
     }
     // (dtype USTRUN_F32X3's first convolution: the streaming kernel with three-term products)
     if (dtype == USTRUN_F32X3 && nsrc == 1 && conv_first_supported(srcs[0], Cout) && srcs[0].H == H && srcs[0].W == W && srcs[0].f32 &&
-        9 * srcs[0].C <= 32 && conv_first_wgrad_stream_ok(srcs[0], N, H, W, 4) && !(g_debug_flags & (1 << 29)))
+        9 * srcs[0].C <= 32 && conv_first_wgrad_stream_ok(srcs[0], N, H, W, 4) && !(g_debug_flags & X3_DBG_OFF))
         return conv_first_wgrad(srcs[0], dy, 4, N, dw, accumulate, partials, partials_bytes, (hipStream_t)s, true);
     if (dtype == USTRUN_F32X3 && wgrad_x3_supported(a)) {        // all nine taps per block, operands split at staging (x3.hip)
         int per;

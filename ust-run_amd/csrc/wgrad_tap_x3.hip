@@ -6,8 +6,8 @@
 //
 // The tiling and the WgradArgs contract are wgrad_tap_bf16.hip's, the shared parts in tn_gemm.h.  The arithmetic is wgrad_x3_kernel's:
 // both operands are f32 NHWC in HBM; a staged value goes global -> registers -> [BatchNorm affine + ReLU in f32, zero outside the
-// image / the pixel range] -> split4 -> three bf16 planes in LDS, [plane][pixel][channel]; a fragment pair is six MFMAs, smallest
-// terms first, term by term over the wave's accumulators.
+// image / the pixel range: x3_activate<true>] -> split3, store_planes -> three bf16 planes in LDS, [plane][pixel][channel]; a fragment pair
+// is six MFMAs, smallest terms first, term by term over the wave's accumulators (x3_products, rows outer) -- all of x3_split.h.
 //
 // Stage = 32 pixels: LDS 3 planes x 32 x (TM + TN) x 2 B = 48 KB for the 128 x 128 tile, one buffer -- the loads of stage s + 1 are
 // issued before the MFMAs of stage s and split into LDS after them; two blocks per CU (96 of 160 KB) cover each other's splits and
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_tap_x3_kernel(const WgradArgs a,
     const int cl = ci0 + 4 * c4;
     f32x4 asc = {1.f, 1.f, 1.f, 1.f}, ash = {0.f, 0.f, 0.f, 0.f};
     if (S.scale) { asc = *(const f32x4*)(S.scale + cl); ash = *(const f32x4*)(S.shift + cl); }
-    const float floor_ = S.relu ? 0.f : -__builtin_inff();
+    const float floor_ = x3_floor(S.relu);
     const float* sp = S.ptr + cl;
     const int sN = (int)S.sN, sH = (int)S.sH, sW = (int)S.sW;        // element offsets fit 31 bits (host check)
     f32x4 av[AP];
@@ -87,14 +87,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_tap_x3_kernel(const WgradArgs a,
 #pragma unroll
         for (int i = 0; i < AP; ++i) {
             const int row = arow + AROWS * i;
-            f32x4 v = av[i] * asc + ash;                     // BatchNorm affine + ReLU in f32, before the split
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = __builtin_fmaxf(v[q], floor_);
-            if (!((aok >> i) & 1u)) v = (f32x4){0.f, 0.f, 0.f, 0.f};       // padding / the range's tail, applied after the activation
-            u32x2 p0, p1, p2;
-            split4(v, p0, p1, p2);
-            char* dst = As + row * RBA + ((c4 * 8) ^ (seg_swz<RBA>(row) << 6));
-            *(u32x2*)dst = p0; *(u32x2*)(dst + APLANE) = p1; *(u32x2*)(dst + 2 * APLANE) = p2;
+            // BatchNorm affine + ReLU in f32, then padding / the range's tail, before the split
+            store_planes(split3(x3_activate<true>(av[i], asc, ash, floor_, (aok >> i) & 1u)), As + row * RBA + ((c4 * 8) ^ (seg_swz<RBA>(row) << 6)), APLANE);
         }
     };
     // ---- dy items: the same (row, 4-channel group) pattern over pixel-linear rows of Cout floats ----
@@ -114,10 +108,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_tap_x3_kernel(const WgradArgs a,
         for (int i = 0; i < BP; ++i) {
             const int row = brow + BROWS * i;
             const f32x4 v = (k0 + row < kend) ? bv[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
-            u32x2 p0, p1, p2;
-            split4(v, p0, p1, p2);
-            char* dst = Bs + row * RBB + ((b4 * 8) ^ (seg_swz<RBB>(row) << 6));
-            *(u32x2*)dst = p0; *(u32x2*)(dst + BPLANE) = p1; *(u32x2*)(dst + 2 * BPLANE) = p2;
+            store_planes(split3(v), Bs + row * RBB + ((b4 * 8) ^ (seg_swz<RBB>(row) << 6)), BPLANE);
         }
     };
 
@@ -153,17 +144,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_tap_x3_kernel(const WgradArgs a,
 #pragma unroll
                 for (int j = 0; j < NI; ++j) bf[j][p] = tr_frag<RBB, __bf16>(Bs + p * BPLANE, kk * 16, wn * (TN / 2) + 32 * j, lane);
             }
-            // mfma6's order (small terms first), term by term over the wave's accumulators: the six products of one accumulator
-            // stand MI * NI instructions apart instead of back to back
-            constexpr int TA[6] = {0, 1, 2, 0, 1, 0}, TB[6] = {2, 1, 0, 1, 0, 0};
-#pragma unroll
-            for (int q = 0; q < 6; ++q)
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-#pragma unroll
-                    for (int j = 0; j < NI; ++j)
-                        acc[i][j] = SWAP ? X3_MFMA(bf[j][TB[q]], af[i][TA[q]], acc[i][j], 0, 0, 0)
-                                         : X3_MFMA(af[i][TA[q]], bf[j][TB[q]], acc[i][j], 0, 0, 0);
+            x3_products<false, SWAP>(af, bf, acc);        // term by term: an accumulator's products stand MI * NI instructions apart
         }
         __syncthreads();                              // every wave is done reading this stage
         if (more) {
@@ -218,12 +199,11 @@ int launch_tile(const WgradArgs& a, hipStream_t st) {
 }  // namespace
 
 bool wgrad_tap_x3_supported(const WgradArgs& a) {
-    if (g_debug_flags & (1 << 29)) return false;                   // (A/B runs against the f32 matrix-core kernel)
+    if (g_debug_flags & X3_DBG_OFF) return false;                  // (A/B runs against the f32 matrix-core kernel)
     if (a.dy_s != 1 || a.dy_esz != 4 || a.nsrc != 1 || a.ashift < 0 || a.ashift > 1 || a.astep < 1) return false;
     if (!((a.nseg == 1 && a.segw == 1) || (a.nseg == 9 && a.segw == 3))) return false;      // k = 1 or 3
     const SrcDev& s = a.src[0];
-    if (s.esz != 4 || s.sC != 1 || s.pool || s.gN > 0 || s.C != a.Cin) return false;
-    if ((s.sW & 3) || (s.sH & 3) || (s.sN & 3)) return false;                 // 16-byte loads of 4 channels
+    if (!x3_src_ok(s) || s.gN > 0 || s.C != a.Cin) return false;
     if (a.dyH != a.Hb || a.dyW != a.Wb || a.M <= 0 || a.M >= (1L << 24)) return false;      // float-reciprocal pixel decomposition
     if ((long)a.N * s.sN >= (1L << 31) - 64 || a.M * a.Cout >= (1L << 31) - 64) return false;      // 32-bit element offsets
     return a.Cin % 64 == 0 && a.Cout % 64 == 0;

@@ -18,11 +18,12 @@
 //   wgrad_x3_kernel   weight gradient of the 3x3 convolutions, all nine taps per block (the tiling of wgrad_halo_bf16.hip's
 //                     first kernel: a 4 x 16-pixel activation tile against the 6 x 18 dY halo patch, nine accumulators per wave),
 //                     both operands split at staging; one block per CU, 216 MFMAs per wave and tile.
-// Everything else of this dtype (first convolution, ConvTranspose weight gradient, BatchNorm, head, losses) runs the f32 kernels.
+// (conv3x3_x3_kernel, the halo-tiled forward / input gradient, and wgradT_x3_kernel are described where they stand.)  What the
+// kernels share is in x3_split.h: split3 + store_planes, x3_activate, x3_products / mfma6, x3_woff, X3Src; for the host x3_src_ok and
+// space_split_plan.  Everything else of this dtype (first convolution's forward, BatchNorm, head, losses) runs the f32 kernels.
 #include "igemm_tile.h"
 #include "tn_gemm.h"
-#include "x3_split.h"       // split4, mfma6
-#include <type_traits>
+#include "x3_split.h"       // the split, the product schedule, the weight-plane layout, X3Src, the host helpers
 
 namespace ustrun {
 namespace {
@@ -42,7 +43,7 @@ __global__ __launch_bounds__(256) void pack_x3_kernel(const float* __restrict__ 
         split4(lo, a0, a1, a2);
         split4(hi, c0, c1, c2);
         const long plane = (long)(K / 8) * N * 8;
-        __bf16* o = out + (long)s * 3 * plane + ((long)k8 * N + n) * 8;
+        __bf16* o = out + (long)s * 3 * plane + x3_woff(k8, n, N);
         *(u32x4*)o = (u32x4){a0[0], a0[1], c0[0], c0[1]};
         *(u32x4*)(o + plane) = (u32x4){a1[0], a1[1], c1[0], c1[1]};
         *(u32x4*)(o + 2 * plane) = (u32x4){a2[0], a2[1], c2[0], c2[1]};
@@ -83,25 +84,19 @@ __global__ __launch_bounds__(256, 2) void igemm_x3_kernel(const IgemmArgs a, con
     f32x4 av[AR];
     f32x4 asc, ash;
     unsigned aok = 0;
-    int a_relu = 0;
     // Row geometry -- which input pixel a row reads for this tap, whether it lies inside the source, its element offset -- depends
     // on the tap and on the source only, not on the channel chunk: it is formed when one of the two changes (wave-uniform: the
     // sources' widths are multiples of the chunk) instead of for every stage, which had cost as many VALU instructions as the split.
     long goff[AR];
     int cur_seg = -1, cur_second = -1;
-    const float* sptr = nullptr;
-    const float* sscale = nullptr;
-    const float* sshift = nullptr;
-    int cbase = 0;
+    X3Src src = {};
     auto load_stage = [&](int s) {
         const int seg = s / nchunk, c0 = (s - seg * nchunk) * XBK;
         const int second = (a.nsrc == 2 && c0 >= a.src[0].C) ? 1 : 0;
         if (seg != cur_seg || second != cur_second) {
             cur_seg = seg; cur_second = second;
-            const SrcDev S = pick_src(a.src[0], a.src[1], second != 0);
+            const SrcDev S = src.select(a, second != 0, 0);       // (no batched passes here: igemm_x3_supported)
             const int dy = a.d0 + (seg / a.segw) * a.dstep, dx = a.d0 + (seg % a.segw) * a.dstep;
-            sptr = S.ptr; sscale = S.scale; sshift = S.shift; a_relu = S.relu;
-            cbase = second ? a.src[0].C : 0;
             aok = 0;
 #pragma unroll
             for (int i = 0; i < AR; ++i) {
@@ -113,11 +108,10 @@ __global__ __launch_bounds__(256, 2) void igemm_x3_kernel(const IgemmArgs a, con
                 goff[i] = ok ? ri.n * S.sN + (long)ly * S.sH + (long)lx * S.sW : 0;      // (a clamped address: the value is masked at the split)
             }
         }
-        const int cl = c0 + 4 * a_c4 - cbase;
-        asc = (f32x4){1.f, 1.f, 1.f, 1.f}; ash = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (sscale) { asc = *(const f32x4*)(sscale + cl); ash = *(const f32x4*)(sshift + cl); }
+        const int cl = c0 + 4 * a_c4 - src.cbase;
+        src.consts(cl, asc, ash);
 #pragma unroll
-        for (int i = 0; i < AR; ++i) av[i] = *(const f32x4*)(sptr + goff[i] + cl);
+        for (int i = 0; i < AR; ++i) av[i] = *(const f32x4*)(src.ptr + goff[i] + cl);
     };
     // this wave's weight fragments of a stage: [k step][column tile][plane], each lane 8 consecutive k of its column
     u32x4 bfr[2][2][3];
@@ -129,22 +123,15 @@ __global__ __launch_bounds__(256, 2) void igemm_x3_kernel(const IgemmArgs a, con
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int n = n0 + wn * 64 + j * 32 + l31;
-                const long o = ((long)(c0 / 8 + 2 * ks + lh) * a.Cout + (n < a.Cout ? n : 0)) * 8;
+                const long o = x3_woff(c0 / 8 + 2 * ks + lh, n < a.Cout ? n : 0, a.Cout);
 #pragma unroll
                 for (int p = 0; p < 3; ++p) bfr[ks][j][p] = *(const u32x4*)(ws + p * plane + o);
             }
     };
     auto write_stage = [&]() {
 #pragma unroll
-        for (int i = 0; i < AR; ++i) {
-            f32x4 v = av[i] * asc + ash;
-            if (a_relu) v = relu4(v);
-            if (!((aok >> i) & 1u)) v = (f32x4){0.f, 0.f, 0.f, 0.f};
-            u32x2 p0, p1, p2;
-            split4(v, p0, p1, p2);
-            char* dst = As + (a_r0 + 32 * i) * XAP + a_c4 * 8;
-            *(u32x2*)dst = p0; *(u32x2*)(dst + APLANE) = p1; *(u32x2*)(dst + 2 * APLANE) = p2;
-        }
+        for (int i = 0; i < AR; ++i)
+            store_planes(split3(x3_activate<false>(av[i], asc, ash, src.relu, (aok >> i) & 1u)), As + (a_r0 + 32 * i) * XAP + a_c4 * 8, APLANE);
     };
 
     f32x16 acc[2][2];
@@ -170,14 +157,7 @@ __global__ __launch_bounds__(256, 2) void igemm_x3_kernel(const IgemmArgs a, con
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int p = 0; p < 3; ++p) af[i][p] = __builtin_bit_cast(b16x8, *(const u32x4*)(Ap + p * APLANE + i * 32 * XAP + ks * 32));
-            constexpr int TA[6] = {0, 1, 2, 0, 1, 0}, TB[6] = {2, 1, 0, 1, 0, 0};       // mfma6's order, term by term over the four accumulators
-#pragma unroll
-            for (int q = 0; q < 6; ++q)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-                        acc[i][j] = X3_MFMA(af[i][TA[q]], __builtin_bit_cast(b16x8, bfr[ks][j][TB[q]]), acc[i][j], 0, 0, 0);
+            x3_products<true, false>(af, bfr[ks], acc);
         }
         __syncthreads();
     }
@@ -218,17 +198,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_x3_kernel(const IgemmArgs a, c
     const int c4 = tid & 7;
     int goff[CIT];                                  // element offsets inside the source (< 2^31: conv3x3_x3_supported)
     unsigned gok = 0;
-    int cur_second = -1, cbase = 0, s_relu = 0;
-    const float* sptr = nullptr;
-    const float* sscale = nullptr;
-    const float* sshift = nullptr;
+    int cur_second = -1;
+    X3Src src = {};
     auto geometry = [&](int second) {
         cur_second = second;
-        const SrcDev S = pick_src(a.src[0], a.src[1], second != 0);
-        // batched passes: a tile lies in one image, its pass picks the BatchNorm constants (gN images per pass, gstride floats apart)
-        const long gofs = (S.scale && S.gN > 0) ? (long)(img / S.gN) * S.gstride : 0;
-        sptr = S.ptr; sscale = S.scale ? S.scale + gofs : nullptr; sshift = S.shift ? S.shift + gofs : nullptr; s_relu = S.relu;
-        cbase = second ? a.src[0].C : 0;
+        const SrcDev S = src.select(a, second != 0, img);        // batched passes: a tile lies in one image, whose pass picks the constants
         gok = 0;
 #pragma unroll
         for (int i = 0; i < CIT; ++i) {
@@ -246,25 +220,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_x3_kernel(const IgemmArgs a, c
         const int c0 = c * XBK;
         const int second = (a.nsrc == 2 && c0 >= a.src[0].C) ? 1 : 0;
         if (second != cur_second) geometry(second);
-        const int cl = c0 + 4 * c4 - cbase;
-        asc = (f32x4){1.f, 1.f, 1.f, 1.f}; ash = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (sscale) { asc = *(const f32x4*)(sscale + cl); ash = *(const f32x4*)(sshift + cl); }
+        const int cl = c0 + 4 * c4 - src.cbase;
+        src.consts(cl, asc, ash);
 #pragma unroll
-        for (int i = 0; i < CIT; ++i) av[i] = *(const f32x4*)(sptr + goff[i] + cl);
+        for (int i = 0; i < CIT; ++i) av[i] = *(const f32x4*)(src.ptr + goff[i] + cl);
     };
     auto write_patch = [&]() {
 #pragma unroll
         for (int i = 0; i < CIT; ++i) {
             const int px = (tid + 256 * i) >> 3;
-            if (px < CPP) {
-                f32x4 v = av[i] * asc + ash;
-                if (s_relu) v = relu4(v);
-                if (!((gok >> i) & 1u)) v = (f32x4){0.f, 0.f, 0.f, 0.f};      // zero padding is applied after the activation
-                u32x2 p0, p1, p2;
-                split4(v, p0, p1, p2);
-                char* dst = smem + px * XAP + c4 * 8;
-                *(u32x2*)dst = p0; *(u32x2*)(dst + CPLANE) = p1; *(u32x2*)(dst + 2 * CPLANE) = p2;
-            }
+            if (px < CPP) store_planes(split3(x3_activate<false>(av[i], asc, ash, src.relu, (gok >> i) & 1u)), smem + px * XAP + c4 * 8, CPLANE);
         }
     };
     // weight fragments of step u = 2 tap + (16-channel half) of a chunk: [column tile][plane]
@@ -273,7 +238,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_x3_kernel(const IgemmArgs a, c
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int n = n0 + wn * 64 + j * 32 + l31;
-            const long o = ((long)(c * (XBK / 8) + 2 * (u & 1) + lh) * a.Cout + (n < a.Cout ? n : 0)) * 8;
+            const long o = x3_woff(c * (XBK / 8) + 2 * (u & 1) + lh, n < a.Cout ? n : 0, a.Cout);
 #pragma unroll
             for (int p = 0; p < 3; ++p) b[j][p] = *(const u32x4*)(ws + p * plane + o);
         }
@@ -306,7 +271,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_x3_kernel(const IgemmArgs a, c
         if (c + 1 < nchunk) fetch(c + 1);             // registers, in flight under the nine taps below
 #pragma unroll
         for (int u = 0; u < 18; ++u) {
-            constexpr int dummy = 0; (void)dummy;
             const int un = u + NSET - 1;              // the step whose fragments load under this one's MFMAs
             if (un < 18) load_b(bfr[un % NSET], c, un);
             else if (c + 1 < nchunk) load_b(bfr[un % NSET], c + 1, un - 18);
@@ -322,16 +286,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_x3_kernel(const IgemmArgs a, c
             for (int i = 0; i < RT; ++i)
 #pragma unroll
                 for (int p = 0; p < 3; ++p) af[i][p] = __builtin_bit_cast(b16x8, *(const u32x4*)(At + p * CPLANE + 2 * i * CPW * XAP + ks * 32));
-            // term by term over all of the wave's accumulators: the six products of one accumulator (small terms first, as in mfma6)
-            // stand 2 RT instructions apart instead of back to back
-            constexpr int TA[6] = {0, 1, 2, 0, 1, 0}, TB[6] = {2, 1, 0, 1, 0, 0};
-#pragma unroll
-            for (int q = 0; q < 6; ++q)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int i = 0; i < RT; ++i)
-                        acc[i][j] = X3_MFMA(af[i][TA[q]], __builtin_bit_cast(b16x8, bfr[u % NSET][j][TB[q]]), acc[i][j], 0, 0, 0);
+            x3_products<true, false>(af, bfr[u % NSET], acc);       // term by term: an accumulator's products stand 2 RT instructions apart
         }
     }
 
@@ -391,14 +346,14 @@ constexpr int RB = 192;                                              // LDS row 
 constexpr int WAIT = TH * TW * 16 / 256;                             // float4 items per thread: activation 4,
 constexpr int WDIT = (HP * 16 + 255) / 256;                          //                          dY 7
 
-// Consumer / producer waves (as the 64 -> 64 streaming kernel of round 3): waves 0-3 read fragments and multiply, waves 4-7 fetch,
+// Consumer / producer waves (as the 64 -> 64 streaming kernel of conv_ws64_bf16.hip): waves 0-3 read fragments and multiply, waves 4-7 fetch,
 // activate, split and write the NEXT tile into the other of two stage buffers -- one of each per SIMD, so the ~430 VALU instructions of
 // splitting a tile run under the other wave's 216 MFMAs instead of in front of them (one block of four waves per CU did both in turn:
 // the matrix pipe idled through every split and its two barriers).  Rows are 128 bytes with the 64-byte halves swapped where bit 1 of
 // the row is set (the four rows of a transposing read stay on disjoint bank quarters without the 64 bytes of padding per row that
 // left LDS for ONE stage only).
 constexpr int RBW = 128;
-constexpr int WDROWS = (HP * 16 + 255) / 256 * 16;            // 112: every staging item of the dY patch has a row (108 .. 111: slack, never read)
+constexpr int WDROWS = WDIT * 16;                             // 112: every staging item of the dY patch has a row (108 .. 111: slack, never read)
 constexpr int WATILE2 = TH * TW * RBW, WDTILE2 = WDROWS * RBW, WSTAGE2 = 3 * (WATILE2 + WDTILE2);
 
 // grid = (ci tiles * co tiles, ksplit); tiles_per = spatial tiles per split
@@ -426,10 +381,12 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3_kernel(const WgradArgs a, con
         const int c4 = ptid & 15;
         const int cg = ci0 + 4 * c4;
         const bool second = (a.nsrc == 2 && cg >= a.src[0].C);
+        // (not X3Src: a thread's source never changes, so it is picked once, and the constants are reloaded only when the pass group
+        // changes; X3Src::select per tile would repeat the pick and the division in the producer waves)
         const SrcDev S = pick_src(a.src[0], a.src[1], second);
         const int cl = cg - (second ? a.src[0].C : 0);
         f32x4 asc = {1.f, 1.f, 1.f, 1.f}, ash = {0.f, 0.f, 0.f, 0.f};
-        int cur_grp = -1;                              // batched passes: the constants follow the image of the tile being fetched
+        int cur_grp = -1;                              // batched passes: the constants follow the image of the tile being split
         auto load_consts = [&](int img) {
             const int grp = S.gN > 0 ? img / S.gN : 0;
             if (S.scale && grp != cur_grp) {
@@ -438,7 +395,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3_kernel(const WgradArgs a, con
                 cur_grp = grp;
             }
         };
-        const float a_floor = S.relu ? 0.f : -__builtin_inff();
+        const float a_floor = x3_floor(S.relu);
         const float* sp = S.ptr + cl;
         const float* dyp = a.dy + co0 + 4 * c4;
         f32x4 av[WAIT], dv[WDIT];
@@ -489,23 +446,13 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3_kernel(const WgradArgs a, con
 #pragma unroll
             for (int i = 0; i < WAIT; ++i) {
                 const int px = (ptid + 256 * i) >> 4;
-                f32x4 v = av[i] * asc + ash;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = __builtin_fmaxf(v[q], a_floor);
-                if (!((aok >> i) & 1u)) v = (f32x4){0.f, 0.f, 0.f, 0.f};       // padding is applied after the activation
-                u32x2 p0, p1, p2;
-                split4(v, p0, p1, p2);
-                char* dst = stage + px * RBW + ((c4 * 8) ^ (((px >> 1) & 1) << 6));
-                *(u32x2*)dst = p0; *(u32x2*)(dst + WATILE2) = p1; *(u32x2*)(dst + 2 * WATILE2) = p2;
+                store_planes(split3(x3_activate<true>(av[i], asc, ash, a_floor, (aok >> i) & 1u)), stage + px * RBW + ((c4 * 8) ^ (((px >> 1) & 1) << 6)), WATILE2);
             }
 #pragma unroll
             for (int i = 0; i < WDIT; ++i) {
                 const int hp = (ptid + 256 * i) >> 4;
                 const f32x4 v = ((aok >> (8 + i)) & 1u) ? dv[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
-                u32x2 p0, p1, p2;
-                split4(v, p0, p1, p2);
-                char* dst = stage + 3 * WATILE2 + hp * RBW + ((c4 * 8) ^ (((hp >> 1) & 1) << 6));      // (hp >= HP: the slack rows)
-                *(u32x2*)dst = p0; *(u32x2*)(dst + WDTILE2) = p1; *(u32x2*)(dst + 2 * WDTILE2) = p2;
+                store_planes(split3(v), stage + 3 * WATILE2 + hp * RBW + ((c4 * 8) ^ (((hp >> 1) & 1) << 6)), WDTILE2);      // (hp >= HP: the slack rows)
             }
         };
         if (tbeg < tend) {
@@ -546,7 +493,6 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3_kernel(const WgradArgs a, con
         for (int pr = 0; pr < TH + 2; ++pr) {
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
-                constexpr int dummy = 0; (void)dummy;
                 const int k0 = pr * HW2 + 2 - kw;
                 b16x8 b[3];
 #pragma unroll
@@ -622,23 +568,14 @@ __global__ __launch_bounds__(256, 1) void wgradT_x3_kernel(const WgradArgs a, co
 #pragma unroll
         for (int i = 0; i < UAIT; ++i) {
             const int px = (tid + 256 * i) >> 4;
-            f32x4 v = av[i] * asc + ash;
-            if (S.relu) v = relu4(v);
-            if (!((aok >> i) & 1u)) v = (f32x4){0.f, 0.f, 0.f, 0.f};
-            u32x2 p0, p1, p2;
-            split4(v, p0, p1, p2);
-            char* dst = As + px * RB + c4 * 8;
-            *(u32x2*)dst = p0; *(u32x2*)(dst + UATILE) = p1; *(u32x2*)(dst + 2 * UATILE) = p2;
+            store_planes(split3(x3_activate<false>(av[i], asc, ash, S.relu, (aok >> i) & 1u)), As + px * RB + c4 * 8, UATILE);
         }
 #pragma unroll
         for (int i = 0; i < UDIT; ++i) {
             const int hr = (tid + 256 * i) >> 4;
             const int hy = hr >> 5, hx = hr & 31;
             const int tap = (hy & 1) * 2 + (hx & 1), px = (hy >> 1) * TW + (hx >> 1);
-            u32x2 p0, p1, p2;
-            split4(dv[i], p0, p1, p2);
-            char* dst = Ds + (tap * UPX + px) * RB + c4 * 8;
-            *(u32x2*)dst = p0; *(u32x2*)(dst + UDTILE) = p1; *(u32x2*)(dst + 2 * UDTILE) = p2;
+            store_planes(split3(dv[i]), Ds + (tap * UPX + px) * RB + c4 * 8, UDTILE);
         }
     };
 
@@ -702,20 +639,17 @@ int pack_x3(const float* w_packed, int S, int K, int N, hipStream_t st) {
 }
 
 bool igemm_x3_supported(const IgemmArgs& a) {
-    if (g_debug_flags & (1 << 29)) return false;                   // (A/B runs against the f32 matrix-core kernel)
+    if (g_debug_flags & X3_DBG_OFF) return false;                  // (A/B runs against the f32 matrix-core kernel)
     if (a.Cin % XBK || a.out_esz != 4 || a.M <= 0) return false;
     if (a.nsrc == 2 && a.src[0].C % XBK) return false;             // a chunk never straddles the two sources
-    for (int i = 0; i < a.nsrc; ++i) {
-        const SrcDev& s = a.src[i];
-        if (s.esz != 4 || s.sC != 1 || (s.C & 3) || s.pool) return false;     // (batched passes, gN > 0: the halo-tiled kernel only -- igemm.hip)
-        if ((s.sN | s.sH | s.sW) & 3) return false;                // 16-byte loads
-    }
+    for (int i = 0; i < a.nsrc; ++i)
+        if (!x3_src_ok(a.src[i])) return false;                    // (batched passes, gN > 0: the halo-tiled kernel only -- igemm.hip)
     return true;
 }
 
 // the halo-tiled kernel: a plain 3x3 convolution (forward, or the input gradient's mirrored taps) without output stride / parity
 bool conv3x3_x3_supported(const IgemmArgs& a) {
-    if (!igemm_x3_supported(a) || (g_debug_flags & (1 << 30))) return false;      // (bit 30: the generic x3 kernel, for A/B runs)
+    if (!igemm_x3_supported(a) || (g_debug_flags & X3_DBG_GENERIC)) return false;      // (the generic x3 kernel, for A/B runs)
     if (a.nseg != 9 || a.segw != 3 || a.nz != 1 || a.s_in != 1 || a.s_out != 1 || a.bias) return false;
     if (!((a.d0 == -1 && a.dstep == 1) || (a.d0 == 1 && a.dstep == -1))) return false;
     if (a.Ho != a.Hb || a.Wo != a.Wb) return false;
@@ -753,65 +687,52 @@ int igemm_x3_launch(const IgemmArgs& a, hipStream_t st) {
 }
 
 bool wgrad_x3_supported(const WgradArgs& a) {
-    if (g_debug_flags & (1 << 29)) return false;
+    if (g_debug_flags & X3_DBG_OFF) return false;
     if (a.nseg != 9 || a.segw != 3 || a.d0 != -1 || a.astep != 1 || a.dy_s != 1 || a.ashift != 0 || a.dy_esz != 4) return false;
     if (a.Cin % 64 || a.Cout % 64 || a.dyH != a.Hb || a.dyW != a.Wb) return false;
     for (int i = 0; i < a.nsrc; ++i) {
         const SrcDev& s = a.src[i];
-        if (s.esz != 4 || s.sC != 1 || (s.C & 3) || s.pool) return false;
-        if ((s.sN | s.sH | s.sW) & 3) return false;
+        if (!x3_src_ok(s)) return false;
         if (s.sN >= (1L << 31) - 64 || (s.H + 8L) * s.sH >= (1L << 31) - 64) return false;      // 32-bit element offsets inside an image
     }
     if ((long)(a.dyH + 8) * a.dyW * a.Cout >= (1L << 31) - 64) return false;
     return true;
 }
 
-// split-K over space: one block per CU (98 KB of LDS each), slabs == ksplit
-int wgrad_x3_plan(const WgradArgs& a, int* ksplit, int* tiles_per) {
-    const long pairs = (long)(a.Cin / 64) * (a.Cout / 64);
-    const int ttotal = a.N * cdiv(a.Hb, TH) * cdiv(a.Wb, TW);
-    long ks = (256 + pairs - 1) / pairs;
-    if (ks > ttotal / 4) ks = ttotal / 4;
-    if (ks < 1) ks = 1;
-    const int per = cdiv(ttotal, ks);
-    *tiles_per = per; *ksplit = cdiv(ttotal, per);
-    return 0;
-}
-
 bool wgradT_x3_supported(const WgradArgs& a) {
-    if (g_debug_flags & (1 << 29)) return false;
+    if (g_debug_flags & X3_DBG_OFF) return false;
     if (a.nseg != 4 || a.segw != 2 || a.dy_s != 2 || a.astep != 0 || a.d0 != 0 || a.ashift != 0 || a.dy_esz != 4 || a.nsrc != 1) return false;
     const SrcDev& s = a.src[0];
-    if (s.esz != 4 || s.sC != 1 || s.pool || s.off_y || s.off_x || s.LH != a.Hb || s.LW != a.Wb || s.gN > 0) return false;
-    if ((s.sN | s.sH | s.sW) & 3) return false;
+    if (!x3_src_ok(s) || s.C != a.Cin || s.off_y || s.off_x || s.LH != a.Hb || s.LW != a.Wb || s.gN > 0) return false;
     return a.Cin % 64 == 0 && a.Cout % 64 == 0 && a.dyH == 2 * a.Hb && a.dyW == 2 * a.Wb;
 }
-int wgradT_x3_plan(const WgradArgs& a, int* ksplit, int* tiles_per) {
-    const long pairs = (long)(a.Cin / 64) * (a.Cout / 64);
-    const int ttotal = a.N * cdiv(a.Hb, UTH) * cdiv(a.Wb, TW);
-    long ks = (256 + pairs - 1) / pairs;
-    if (ks > ttotal / 8) ks = ttotal / 8;
-    if (ks < 1) ks = 1;
-    const int per = cdiv(ttotal, ks);
-    *tiles_per = per; *ksplit = cdiv(ttotal, per);
+
+// Both all-taps kernels: split-K over space, 64 x 64 (ci, co) tile pairs, one block per CU (98 KB of LDS each for the 3x3 kernel),
+// slabs == ksplit; a block walks at least 4 tiles of 4 x 16 pixels (3x3) / 8 tiles of 2 x 16 (ConvTranspose).
+int wgrad_x3_plan(const WgradArgs& a, int* ksplit, int* tiles_per) {
+    space_split_plan((long)(a.Cin / 64) * (a.Cout / 64), a.N * cdiv(a.Hb, TH) * cdiv(a.Wb, TW), 4, ksplit, tiles_per);
     return 0;
 }
-int wgradT_x3_launch(const WgradArgs& a, int ksplit, int tiles_per, hipStream_t st) {
-    const int lds = 3 * (UATILE + UDTILE);
-    USTRUN_TRY(ensure_dynamic_lds((const void*)wgradT_x3_kernel, lds, "wgradT_x3"));
-    dim3 grid((a.Cin / 64) * (a.Cout / 64), ksplit), block(256);
-    hipLaunchKernelGGL(wgradT_x3_kernel, grid, block, lds, st, a, a.Cout / 64, cdiv(a.Wb, TW), cdiv(a.Hb, UTH), tiles_per);
-    USTRUN_LAUNCH_CHECK("wgradT_x3");
+int wgradT_x3_plan(const WgradArgs& a, int* ksplit, int* tiles_per) {
+    space_split_plan((long)(a.Cin / 64) * (a.Cout / 64), a.N * cdiv(a.Hb, UTH) * cdiv(a.Wb, TW), 8, ksplit, tiles_per);
     return 0;
 }
 
-int wgrad_x3_launch(const WgradArgs& a, int ksplit, int tiles_per, hipStream_t st) {
-    const int lds = 2 * WSTAGE2;
-    USTRUN_TRY(ensure_dynamic_lds((const void*)wgrad_x3_kernel, lds, "wgrad_x3"));
-    dim3 grid((a.Cin / 64) * (a.Cout / 64), ksplit), block(512);
-    hipLaunchKernelGGL(wgrad_x3_kernel, grid, block, lds, st, a, a.Cout / 64, cdiv(a.Wb, TW), cdiv(a.Hb, TH), tiles_per);
-    USTRUN_LAUNCH_CHECK("wgrad_x3");
+namespace {
+template <void (*KERNEL)(WgradArgs, int, int, int, int), int THREADS, int TILE_H, int LDS>
+int launch_space_split(const WgradArgs& a, int ksplit, int tiles_per, hipStream_t st, const char* who) {
+    USTRUN_TRY(ensure_dynamic_lds((const void*)KERNEL, LDS, who));
+    dim3 grid((a.Cin / 64) * (a.Cout / 64), ksplit), block(THREADS);
+    hipLaunchKernelGGL(KERNEL, grid, block, LDS, st, a, a.Cout / 64, cdiv(a.Wb, TW), cdiv(a.Hb, TILE_H), tiles_per);
+    USTRUN_LAUNCH_CHECK(who);
     return 0;
+}
+}  // namespace
+int wgrad_x3_launch(const WgradArgs& a, int ksplit, int tiles_per, hipStream_t st) {
+    return launch_space_split<wgrad_x3_kernel, 512, TH, 2 * WSTAGE2>(a, ksplit, tiles_per, st, "wgrad_x3");
+}
+int wgradT_x3_launch(const WgradArgs& a, int ksplit, int tiles_per, hipStream_t st) {
+    return launch_space_split<wgradT_x3_kernel, 256, UTH, 3 * (UATILE + UDTILE)>(a, ksplit, tiles_per, st, "wgradT_x3");
 }
 
 }  // namespace ustrun
