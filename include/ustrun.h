@@ -416,6 +416,52 @@ int ustrun_row_kl_fwd(const float* a, const float* b, int64_t rows, int C, float
 int ustrun_row_kl_bwd(const float* a, const float* b, int64_t rows, int C, const float* gout_dev, float* da, float* db,
                       ustrun_stream_t s);
 
+/* ---- label-map losses and metrics (csrc/labelmap.hip) -----------------------------------------------------------------------
+ * Class-weighted cross-entropy of f32 logits [N,K,HW], K = 1..USTRUN_CE_MAP_KMAX, against an int64 label map [N,HW]: replaces
+ * cross_entropy2d of utils/metrics.py:93-111 and of dataloaders/utils.py:128-144.  weight_dev: K device floats or NULL (ones).
+ * A pixel is ignored if has_ignore and t == ignore_index, or if ignore_negative and t < 0; a target that is not ignored and lies
+ * outside [0,K) contributes nothing and is counted.  One pass over the planes with an online log-sum-exp; four pixels per lane
+ * with 16-byte accesses when HW % 4 == 0 and every pointer is 16-byte aligned, one pixel otherwise (same arithmetic).
+ *   out[0] = scale * S (/ out[2] if by_weight) (/ out[3] if by_count),  out[1] = S = sum w[t] (lse - x_t),  out[2] = sum w[t],
+ *   out[3] = valid pixels,  out[4] = out-of-range targets;  lse[N,HW] = the log-sum-exp of every pixel (NULL skips it).
+ * No valid pixel: nan with either divisor, 0 without.  partials as ustrun_loss_partials_bytes; a repeated call is bit-identical.
+ * bwd: dlogits[n,k,hw] = gout_dev[0] * coef * w[t] * (exp(x_k - lse) - [k == t]) on valid pixels and exactly 0 elsewhere, coef
+ * from scale, the two flags and fwd_out (the forward's out, read on the device); lse is the forward's map.               */
+#define USTRUN_CE_MAP_NOUT 5
+#define USTRUN_CE_MAP_KMAX 256
+int ustrun_ce_map_fwd(const float* logits, const int64_t* target, const float* weight_dev, int N, int K, int HW, int has_ignore,
+                      int64_t ignore_index, int ignore_negative, float scale, int by_weight, int by_count, float* out, float* lse,
+                      float* partials, int64_t partials_bytes, ustrun_stream_t s);
+int ustrun_ce_map_bwd(const float* logits, const int64_t* target, const float* weight_dev, const float* lse, int N, int K, int HW,
+                      int has_ignore, int64_t ignore_index, int ignore_negative, float scale, int by_weight, int by_count,
+                      const float* fwd_out, const float* gout_dev, float* dlogits, ustrun_stream_t s);
+
+/* Confusion matrices of two label maps [N,HW] (int64 or f32 class indices, as ustrun_dice_counts takes them), K = 1..
+ * USTRUN_CONFUSION_KMAX, HW < 2^31: counts[n][g][p] (int32, row = gt, column = pred); skipped[n] = pixels whose gt equals
+ * ignore_index (has_ignore) or where either label is outside [0,K) (an f32 label that is no integer counts as outside).  Both
+ * outputs are zeroed by the call; integer atomics only, so the result does not depend on scheduling.  The counts carry get_iou
+ * and get_dice of dataloaders/utils.py:150-188 and cal_dice of utils/metrics.py:13-24 with no other pass over the maps.  */
+#define USTRUN_CONFUSION_KMAX 32
+int ustrun_confusion(const void* pred, const void* gt, int pred_is_i64, int gt_is_i64, int N, int K, int64_t HW, int has_ignore,
+                     int64_t ignore_index, int32_t* counts, int32_t* skipped, ustrun_stream_t s);
+
+/* Four sums per class plane of x, t (f32 [N,K,HW], K = 1..8) over N and HW, s = x (act USTRUN_LOSS_SOFTMAX: no activation) or
+ * sigmoid(x) (USTRUN_LOSS_SIGMOID); where has_ignore and t == ignore_value both operands count as 0 (utils/metrics.py:41-44):
+ *   out[k] = {sum s t, sum s, sum t, sum (1 + t) bce_with_logits(x, t)}   (the last only with the sigmoid, else 0)
+ * They carry dice, DiceLoss, Balanced_DiceLoss and WatershedCrossEntropy of utils/metrics.py:36-47,72-91,242-266.
+ * bwd: dx = (coef[k][0] t + coef[k][1]) ds/dx + coef[k][2] (1 + t)(s - t), 0 where t is ignored; coef_dev = K x 3 device floats. */
+int ustrun_plane_sums_fwd(const float* x, const float* t, int N, int K, int HW, int act, int has_ignore, float ignore_value, float* out,
+                          float* partials, int64_t partials_bytes, ustrun_stream_t s);
+int ustrun_plane_sums_bwd(const float* x, const float* t, int N, int K, int HW, int act, int has_ignore, float ignore_value,
+                          const float* coef_dev, float* dx, ustrun_stream_t s);
+
+/* Colour decoding of label maps [N,HW] (int64 or f32), decode_segmap of dataloaders/utils.py:86-120: out f32 [N,3,HW] =
+ * palette[l][c] / 255 with palette_dev K x 3 device bytes, K = 1..USTRUN_COLORIZE_KMAX; a label outside [0,K) writes l / 255 in
+ * all three channels, the value the reference's copies leave there (:105-115).                                          */
+#define USTRUN_COLORIZE_KMAX 256
+int ustrun_colorize(const void* labels, int labels_is_i64, int N, int HW, const uint8_t* palette_dev, int K, float* out,
+                    ustrun_stream_t s);
+
 /* ---- per-sample binary overlap counts for the numpy Dice of utils/metrics.py:114-146 ---------
  * counts[n][c] = {|pred|, |gt|, |pred & gt|} with pred/gt binarised as (x == cls[c]) or (x != 0). */
 int ustrun_dice_counts(const void* pred, const void* gt, int pred_is_i64, int gt_is_i64, int N,

@@ -12,14 +12,6 @@ namespace {
 constexpr float DICE_SMOOTH = 1e-5f;      // losses.py:10,21
 constexpr float ENT_EPS = 1e-6f;          // losses.py:32,60,272,279
 
-template <int V> __device__ __forceinline__ void ldv(const float* p, float (&o)[V]) {
-    if constexpr (V == 4) { const f32x4 t = *(const f32x4*)p; o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w; }
-    else o[0] = *p;
-}
-template <int V> __device__ __forceinline__ void stv(float* p, const float (&o)[V]) {
-    if constexpr (V == 4) *(f32x4*)p = (f32x4){o[0], o[1], o[2], o[3]};
-    else *p = o[0];
-}
 template <int V, int KN> __device__ __forceinline__ void ld_planes(const float* t, long n, int K, int HW, long hw, float (&x)[KN][V]) {
 #pragma unroll
     for (int k = 0; k < KN; ++k) if (k < K) ldv<V>(t + (n * K + k) * HW + hw, x[k]);
@@ -64,23 +56,6 @@ template <int KN> __device__ __forceinline__ void through_act(int act, int K, co
 #pragma unroll
         for (int k = 0; k < KN; ++k) if (k < K) G[k] = G[k] * p[k] * (1.f - p[k]);
     }
-}
-
-// the first NC running sums of every thread -> the block's partial row (rows are NS floats apart)
-template <int NC> __device__ __forceinline__ void block_row(const float (&acc)[NC], float* __restrict__ partials) {
-    __shared__ float red[4][NC];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NC; ++i) { const float v = wave_sum(acc[i]); if (lane == 0) red[wave][i] = v; }
-    __syncthreads();
-    if (threadIdx.x < NC)
-        partials[(long)blockIdx.x * NS + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-}
-
-// item i of a [N, HW / V] walk -> image and first pixel (32-bit divide: N * HW < 2^32, checked on the host)
-template <int V> __device__ __forceinline__ void item_at(long i, int per, long& n, long& hw) {
-    n = (unsigned)i / (unsigned)per;
-    hw = (i - n * per) * V;
 }
 
 // ---- pair consistency ----------------------------------------------------------------------------------------------------
@@ -434,8 +409,6 @@ int finalize(const float* partials, int rows, int ncols, int what, int K, double
     USTRUN_LAUNCH_CHECK(who);
     return 0;
 }
-
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int shape_ok(const char* who, int N, int K, int HW) {
     USTRUN_CHECK(K >= 1 && K <= KMAX, "%s: %d classes (1..%d)", who, K, KMAX);

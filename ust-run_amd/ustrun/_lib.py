@@ -12,6 +12,7 @@ F32, BF16, F16, F32X3 = 0, 1, 2, 3
 LOSS_SOFTMAX, LOSS_SIGMOID = 0, 1
 CONS_MSE_MAP, CONS_KL_MEAN, CONS_SOFT_DICE, CONS_NOUT = 0, 1, 2, 25
 PAIR_DICE_SQ, PAIR_DICE, PAIR_MSE, PAIR_NOUT = 0, 1, 2, 9
+CE_MAP_NOUT, CE_MAP_KMAX, CONFUSION_KMAX, COLORIZE_KMAX = 5, 256, 32, 256
 
 vp, fp, i32, i64, f32 = C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -149,6 +150,12 @@ SIGNATURES = {
     "ustrun_pair_sums_bwd": (i32, [fp, fp, i64, i32, fp, fp, fp, fp, vp]),
     "ustrun_row_kl_fwd": (i32, [fp, fp, i64, i32, fp, fp, i64, vp]),
     "ustrun_row_kl_bwd": (i32, [fp, fp, i64, i32, fp, fp, fp, vp]),
+    "ustrun_ce_map_fwd": (i32, [fp, vp, fp, i32, i32, i32, i32, i64, i32, f32, i32, i32, fp, fp, fp, i64, vp]),
+    "ustrun_ce_map_bwd": (i32, [fp, vp, fp, fp, i32, i32, i32, i32, i64, i32, f32, i32, i32, fp, fp, fp, vp]),
+    "ustrun_confusion": (i32, [vp, vp, i32, i32, i32, i32, i64, i32, i64, vp, vp, vp]),
+    "ustrun_plane_sums_fwd": (i32, [fp, fp, i32, i32, i32, i32, i32, f32, fp, fp, i64, vp]),
+    "ustrun_plane_sums_bwd": (i32, [fp, fp, i32, i32, i32, i32, i32, f32, fp, fp, vp]),
+    "ustrun_colorize": (i32, [vp, i32, i32, i32, vp, i32, fp, vp]),
     "ustrun_debug_conv_stat_rows": (i32, [i32] * 10),
     "ustrun_debug_last_wgrad_variant": (i32, []),
     "ustrun_debug_flags": (i32, [i32]),

@@ -383,6 +383,172 @@ def class_dice(logits, target, act="none", weight=None, smooth=1e-5):
     return _ClassDiceFn.apply(logits, target, act, weight, float(smooth))
 
 
+# ---- label-map losses and metrics (csrc/labelmap.hip) ---------------------------------------------------------------------------
+def _label_map(t, name, numel=None):
+    if not t.is_cuda or t.dtype not in (torch.int64, torch.float32):
+        raise RuntimeError(f"{name}: expected an int64 or float32 HIP tensor of class indices, got {t.dtype} on {t.device}")
+    if numel is not None and t.numel() != numel:
+        raise RuntimeError(f"{name}: {tuple(t.shape)} does not hold {numel} labels")
+    return t.contiguous()
+
+
+def _ce_map_args(logits, target, weight, ignore_index, ignore_negative, scale, by_weight, by_count):
+    logits = _f32c(logits, "ce_map: logits")
+    N, K, HW = _nkhw(logits, "ce_map: logits")
+    if target.dtype != torch.int64 or not target.is_cuda or target.numel() != N * HW:
+        raise RuntimeError(f"ce_map: target must be an int64 HIP tensor with N*H*W = {N * HW} elements, got {target.dtype} {tuple(target.shape)} on {target.device}")
+    if weight is not None:
+        weight = _f32c(weight, "ce_map: weight")
+        if weight.numel() != K:
+            raise RuntimeError(f"ce_map: weight has {weight.numel()} entries for {K} classes")
+    cfg = (N, K, HW, int(ignore_index is not None), int(ignore_index or 0), int(bool(ignore_negative)), float(scale), int(bool(by_weight)),
+           int(bool(by_count)))
+    return logits, target.contiguous(), weight, cfg
+
+
+def _ce_map_run(*args):
+    logits, target, weight, cfg = _ce_map_args(*args)
+    N, K, HW = cfg[:3]
+    out = torch.empty(L.CE_MAP_NOUT, dtype=torch.float32, device=logits.device)
+    lse = torch.empty((N, HW), dtype=torch.float32, device=logits.device)
+    part, nb = _partials(logits.device)
+    L.check(L.lib().ustrun_ce_map_fwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), *cfg, out.data_ptr(), lse.data_ptr(), part.data_ptr(), nb,
+                                      stream_ptr()), "ustrun_ce_map_fwd")
+    return logits, target, weight, cfg, out, lse
+
+
+def ce_map_stats(logits, target, weight=None, ignore_index=None, ignore_negative=False, scale=1.0, by_weight=False, by_count=False):
+    """The forward of `ce_map` with everything it writes, outside autograd: (out, lse) with out = {loss, S = sum w[t] (lse - x_t),
+    sum w[t], valid pixels, out-of-range targets} (L.CE_MAP_NOUT device floats) and lse the per-pixel log-sum-exp [N,HW]."""
+    return _ce_map_run(logits.detach(), target, weight, ignore_index, ignore_negative, scale, by_weight, by_count)[4:]
+
+
+class _CeMapFn(torch.autograd.Function):
+    """cross_entropy2d of utils/metrics.py:93-111 and dataloaders/utils.py:128-144 through ustrun_ce_map_fwd/_bwd; the per-pixel
+    log-sum-exp is saved for the backward (one float per pixel against a second read of all K planes)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, ignore_negative, scale, by_weight, by_count):
+        logits, target, weight, cfg, out, lse = _ce_map_run(logits, target, weight, ignore_index, ignore_negative, scale, by_weight, by_count)
+        ctx.save_for_backward(logits, target, lse, out, *(() if weight is None else (weight,)))
+        ctx.cfg = cfg
+        return out[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        logits, target, lse, out = ctx.saved_tensors[:4]
+        weight = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+        dl, g = torch.empty_like(logits), _upstream(g)
+        L.check(L.lib().ustrun_ce_map_bwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), lse.data_ptr(), *ctx.cfg, out.data_ptr(), g.data_ptr(),
+                                          dl.data_ptr(), stream_ptr()), "ustrun_ce_map_bwd")
+        return dl, None, None, None, None, None, None, None
+
+
+def ce_map(logits, target, weight=None, ignore_index=None, ignore_negative=False, scale=1.0, by_weight=False, by_count=False):
+    """Class-weighted cross-entropy of logits [N,K,...] (K up to 256) against an int64 label map, differentiable in the logits:
+    scale * sum w[t] (lse - x_t) over the pixels that count, divided by sum w[t] (by_weight) and / or by their number (by_count).
+    A pixel does not count if t == ignore_index or, with ignore_negative, t < 0; a target outside [0,K) that is not ignored adds
+    nothing (ce_map_stats reports how many there were).  weight: K device floats.  No valid pixel: nan with a divisor, else 0."""
+    return _CeMapFn.apply(logits, target, weight, ignore_index, bool(ignore_negative), float(scale), bool(by_weight), bool(by_count))
+
+
+def confusion(pred, gt, n_classes, ignore_index=None):
+    """Confusion matrices of two label maps [N,...] (int64 or float32 class indices): (counts int32 [N,K,K] with row = gt and
+    column = pred, skipped int32 [N] = pixels whose gt is ignore_index or where either label is outside [0,K)).  K up to 32."""
+    N = pred.shape[0]
+    pred = _label_map(pred, "confusion: pred")
+    gt = _label_map(gt, "confusion: gt", pred.numel())
+    K = int(n_classes)
+    counts = torch.empty((N, max(K, 0), max(K, 0)), dtype=torch.int32, device=pred.device)
+    skipped = torch.empty(N, dtype=torch.int32, device=pred.device)
+    L.check(L.lib().ustrun_confusion(pred.data_ptr(), gt.data_ptr(), int(pred.dtype == torch.int64), int(gt.dtype == torch.int64), N, K,
+                                     pred.numel() // max(N, 1), int(ignore_index is not None), int(ignore_index or 0), counts.data_ptr(),
+                                     skipped.data_ptr(), stream_ptr()), "ustrun_confusion")
+    return counts, skipped
+
+
+class _PlaneSumsFn(torch.autograd.Function):
+    """ustrun_plane_sums_fwd/_bwd: the sums are linear in s and in the weighted BCE, so any loss built on them with torch's scalar
+    operators gets its gradient from the three coefficients per plane that autograd hands back."""
+
+    @staticmethod
+    def forward(ctx, x, t, act, ignore_value):
+        x, t = _f32c(x, "plane_sums: input"), _f32c(t, "plane_sums: target")
+        if x.shape != t.shape:
+            raise RuntimeError(f"plane_sums: input {tuple(x.shape)} and target {tuple(t.shape)} differ")
+        N, K, HW = _nkhw(x, "plane_sums: input")
+        out = torch.empty((K, 4), dtype=torch.float32, device=x.device)
+        part, nb = _partials(x.device)
+        ctx.cfg = (N, K, HW, _MODE["sigmoid"] if act == "sigmoid" else _MODE["softmax"], int(ignore_value is not None), float(ignore_value or 0.0))
+        L.check(L.lib().ustrun_plane_sums_fwd(x.data_ptr(), t.data_ptr(), *ctx.cfg, out.data_ptr(), part.data_ptr(), nb, stream_ptr()),
+                "ustrun_plane_sums_fwd")
+        ctx.save_for_backward(x, t)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, t = ctx.saved_tensors
+        g = _upstream(g)
+        coef = torch.stack((g[:, 0], g[:, 1], g[:, 3]), dim=1).contiguous()          # d loss / d {sum s t, sum s, sum (1 + t) bce} per plane
+        dx = torch.empty_like(x)
+        L.check(L.lib().ustrun_plane_sums_bwd(x.data_ptr(), t.data_ptr(), *ctx.cfg, coef.data_ptr(), dx.data_ptr(), stream_ptr()),
+                "ustrun_plane_sums_bwd")
+        return dx, None, None, None
+
+
+def plane_sums(x, t, act="none", ignore_value=None):
+    """Per class plane of x, t [N,K,...] (K up to 8), over N and the pixels: [K,4] = {sum s t, sum s, sum t, sum (1 + t) bce(x, t)}
+    with s = x (act "none") or sigmoid(x) ("sigmoid"; the last column is 0 without it); where t == ignore_value both operands
+    count as 0.  Differentiable in x."""
+    if act not in ("none", "sigmoid"):
+        raise ValueError(f"plane_sums: act {act!r} (none / sigmoid)")
+    return _PlaneSumsFn.apply(x, t, act, ignore_value)
+
+
+def _smooth_dice(rows, smooth=1.0):
+    """[R,4] plane sums -> [R] values of (2 sum s t + smooth) / (sum s + sum t + smooth); whole rows at once: every scalar
+    operator here is a launch of its own, forward and backward"""
+    return (2.0 * rows[:, 0] + smooth) / (rows[:, 1] + rows[:, 2] + smooth)
+
+
+def map_dice(x, t, ignore_value=None):
+    """(2 sum x t + 1) / (sum x + sum t + 1) over every element (dice of utils/metrics.py:36-47; 1 - this is DiceLoss, :242-255)."""
+    return _smooth_dice(plane_sums(x.reshape(1, 1, -1), t.reshape(1, 1, -1), "none", ignore_value))[0]
+
+
+def balanced_dice_loss(x, t):
+    """Balanced_DiceLoss (utils/metrics.py:257-266): half the sum of 1 - dice over the sigmoid of channels 0 and 1."""
+    if x.shape[1] > 2:
+        x, t = x[:, :2], t[:, :2]
+    return 1.0 - 0.5 * _smooth_dice(plane_sums(x, t, "sigmoid")).sum()
+
+
+def watershed_ce(x, t):
+    """mean over N*H*W of sum_{k<2} (1 + t_k) bce_with_logits(x_k, t_k) (WatershedCrossEntropy, utils/metrics.py:72-91, with the
+    weight in the form target + 1 it takes wherever the reference's is finite)."""
+    if x.shape[1] > 2:
+        x, t = x[:, :2], t[:, :2]
+    N, K, HW = _nkhw(x, "watershed_ce: input")
+    return plane_sums(x, t, "sigmoid")[:, 3].sum() / float(N * HW)
+
+
+def colorize(labels, palette):
+    """Label maps [N,...] (int64 or float32 HIP tensor) -> float32 [N,3,...] = palette[l] / 255 with palette a [K,3] uint8 tensor or
+    array (K up to 256); a label outside [0,K) gives l / 255 in all three channels."""
+    labels = _label_map(labels, "colorize: labels")
+    pal = torch.as_tensor(palette)
+    if pal.dim() != 2 or pal.shape[1] != 3 or pal.dtype != torch.uint8:
+        raise RuntimeError(f"colorize: palette must be [K,3] uint8, got {tuple(pal.shape)} {pal.dtype}")
+    pal = pal.to(labels.device).contiguous()
+    N = labels.shape[0]
+    out = torch.empty((N, 3) + tuple(labels.shape[1:]), dtype=torch.float32, device=labels.device)
+    L.check(L.lib().ustrun_colorize(labels.data_ptr(), int(labels.dtype == torch.int64), N, labels.numel() // max(N, 1), pal.data_ptr(), pal.shape[0],
+                                    out.data_ptr(), stream_ptr()), "ustrun_colorize")
+    return out
+
+
 def pseudo_label(logits, threshold, mode):
     """train.py:648-667.  softmax -> (label int64 [N,H,W], mask f32 [N,1,H,W]); sigmoid -> f32 [N,K,H,W] x2."""
     lib = L.lib()

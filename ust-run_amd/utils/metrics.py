@@ -11,6 +11,9 @@ part, the border sizes, the two integer order statistics of the squared surface 
 prediction's distances; the square roots, numpy's linear percentile and the reference's empty-mask rules are applied here.
 
 `distance_transform` is the Euclidean distance transform utils/metrics.py:52-70 means to be, computed on the device.
+
+`cal_dice`, `dice`, `WatershedCrossEntropy`, `cross_entropy2d`, `dice_loss`, `DiceLoss` and `Balanced_DiceLoss` keep the reference's
+signatures and defaults; their arithmetic over tensors runs on the device (ustrun.functional: ce_map, confusion, plane_sums).
 """
 import numpy as np
 
@@ -90,6 +93,83 @@ def distance_transform(bitmap):
     s2, _ = F.signed_dist2(torch.from_numpy((np.asarray(bitmap) != 0).astype(np.float32)).cuda())
     s2 = s2.cpu().numpy()[:, 0]
     return np.where(s2 == F.DIST_NONE, np.inf, np.sqrt(np.maximum(s2, 0).astype(np.float64)))
+
+
+# ---- the label-map losses and metrics of the reference's utils/metrics.py:13-47,72-111,233-266 (ustrun.functional, csrc/labelmap.hip)
+def _labels_on_device(x):
+    """numpy or tensor label map -> (HIP tensor of int64 or float32 class indices, came from numpy)"""
+    import torch
+    is_np = not torch.is_tensor(x)
+    t = torch.from_numpy(np.ascontiguousarray(x)) if is_np else x
+    if t.dtype not in (torch.int64, torch.float32):
+        t = t.float() if t.is_floating_point() else t.long()
+    return t.cuda(), is_np
+
+
+def confusion_counts(pred, gt, n_classes, who):
+    """[N,K,K] int64 numpy confusion matrices (row = gt, column = pred) of two label batches, counted on the device; this waits
+    for the result.  ValueError if a label of either map lies outside [0, n_classes)."""
+    from ustrun import functional as F
+    p, _ = _labels_on_device(pred)
+    g, _ = _labels_on_device(gt)
+    counts, skipped = F.confusion(p, g, n_classes)
+    skipped = skipped.cpu().numpy()
+    if skipped.any():
+        n = int(np.flatnonzero(skipped)[0])
+        raise ValueError(f"{who}: sample {n} has {int(skipped[n])} pixels whose label is not a class index in [0, {n_classes})")
+    return counts.cpu().numpy().astype(np.int64)
+
+
+def cal_dice(prediction, label, num=2):
+    """2 |P_i & L_i| / (|P_i| + |L_i|) for the classes i = 1..num-1 over the whole batch, as a float64 array of num - 1 values
+    (nan for a class absent from both, as the reference's 0 / 0), from one confusion matrix counted on the device.  This is the
+    formula of utils/metrics.py:13-24 restated: the reference's own lines use np.float, which numpy no longer has."""
+    p, g = np.asarray(_np(prediction)), np.asarray(_np(label))
+    c = confusion_counts(p.reshape(1, -1), g.reshape(1, -1), num, "cal_dice")[0].astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return 2.0 * np.diag(c)[1:] / (c.sum(0)[1:] + c.sum(1)[1:])
+
+
+def dice(input, target, ignore_index=None):
+    """(2 sum i t + 1) / (sum i + sum t + 1) over every element, both operands 0 where target == ignore_index
+    (utils/metrics.py:36-47); a device scalar, differentiable in `input`."""
+    from ustrun import functional as F
+    return F.map_dice(input, target, ignore_index)
+
+
+def WatershedCrossEntropy(input, target):
+    """mean over N*H*W of (1 + t_0) bce(x_0, t_0) + (1 + t_1) bce(x_1, t_1) on logits and {0,1} targets [N,2,H,W]
+    (utils/metrics.py:72-91).  The reference's weight, map * (1 - DT / max DT) + 1 with its own distance_transform, equals
+    target + 1 wherever it is finite.  A batch with an empty plane makes the reference's weight nan over that whole plane and its
+    loss nan; this function returns the finite target + 1 form there too."""
+    from ustrun import functional as F
+    return F.watershed_ce(input, target)
+
+
+def cross_entropy2d(input, target, weight=None, size_average=False):
+    """The weighted mean of nll over the pixels with target >= 0 (utils/metrics.py:93-111), divided AGAIN by their number when
+    size_average: the reference divides nll_loss's mean by the count, and so does this.  weight: K device floats or None."""
+    from ustrun import functional as F
+    return F.ce_map(input, target, weight=weight, ignore_negative=True, by_weight=True, by_count=bool(size_average))
+
+
+def dice_loss(pred, target):
+    """1 - dice_coeff(pred, target) on the host (utils/metrics.py:233-239).  For a batch dice_coeff returns a list, and the
+    reference's `1 - list` raises TypeError; this returns the list of 1 - v instead."""
+    d = dice_coeff(pred, target)
+    return [1 - v for v in d] if isinstance(d, list) else 1 - d
+
+
+def DiceLoss(input, target):
+    """1 - (2 sum i t + 1) / (sum i + sum t + 1) over every element (utils/metrics.py:242-255); a device scalar."""
+    from ustrun import functional as F
+    return 1 - F.map_dice(input, target)
+
+
+def Balanced_DiceLoss(input, target):
+    """Half the sum of DiceLoss over the sigmoid of channels 0 and 1 (utils/metrics.py:257-266); a device scalar."""
+    from ustrun import functional as F
+    return F.balanced_dice_loss(input, target)
 
 
 def dice_coefficient_numpy(binary_segmentation, binary_gt_label):
