@@ -76,13 +76,16 @@ def test_conv1x1_production_tiles(ci, co, flags, want):
         lib.ustrun_debug_flags(old)
 
 
+PROD_NHW = (2, 64, 64)        # (tests/test_convT_plan_host.py plans the same launches on the CPU)
+
+
 def _conv1x1_production_tiles(ci, co, want):
     """The bottleneck GEMMs at the shapes DeepLabV2 @512^2 runs them (N = 2, 64 x 64 maps: M = 8192 pixels): BatchNorm affine +
     ReLU on load, bf16 outputs, statistics rows of the stored values; 256 -> 1024 reaches the 256-column tile (18.9 % of the
     forward + backward kernel time in profiles/r02_deeplab_fwdbwd_n8_kernel_stats.csv), 1024 -> 256 the 128-column one."""
     l = L()
     lib = l.lib()
-    n, h, w = 2, 64, 64
+    n, h, w = PROD_NHW
     g = torch.Generator().manual_seed(ci + co)
     y0 = torch.randint(-3, 4, (n, ci, h, w), generator=g).float()
     sc = torch.randint(1, 3, (ci,), generator=g).float()

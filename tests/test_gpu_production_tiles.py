@@ -345,16 +345,30 @@ def test_linear_tiles_shorter_last_pass_exact():
         np.testing.assert_allclose(st[1].numpy(), ys.square().sum((0, 2, 3)).numpy(), rtol=1e-5)
 
 
-@pytest.mark.parametrize("n,G,ci,co,h,w", [
-    (8, 4, 128, 64, 24, 40),                 # the full-resolution level's channel plan, four batched passes, 60 tiles
-    (6, 2, 256, 128, 20, 24),                # 4 K chunks forward / 8 in the gradient, two N tiles forward, a ragged last tile
-    (3, 1, 512, 256, 9, 11),                 # odd extents, M % 128 != 0, 8 K chunks forward / 16 in the gradient, 256-column tiles both ways
-    (8, 2, 128, 64, 128, 128),               # the full-resolution level of the U-Net at its natural extent: 1024 tiles
-])
-def test_convT_bf16_batched_passes_exact(n, G, ci, co, h, w):
+# ustrun_debug_flags 512: the builds with weight tiles in LDS (convT_bf16_kernel<256, 32, 0> forward, <128, 64, 1> gradient at these sizes)
+CONVT_BATCHED_CASES = [
+    # (N, passes, Cin, Cout, H, W, flags)
+    (8, 4, 128, 64, 24, 40, 0),              # the full-resolution level's channel plan, four batched passes, 60 tiles
+    (6, 2, 256, 128, 20, 24, 0),             # 4 K chunks forward / 8 in the gradient, two N tiles forward, a ragged last tile
+    (3, 1, 512, 256, 9, 11, 0),              # odd extents, M % 128 != 0, 8 K chunks forward / 16 in the gradient
+    (8, 2, 128, 64, 128, 128, 0),            # the full-resolution level of the U-Net at its natural extent: 1024 tiles
+    (6, 2, 256, 128, 20, 24, 512),
+    (3, 1, 512, 256, 9, 11, 512),
+]
+
+
+def convT_batched_variants(flags):
+    """(forward, input gradient) codes: 'CT' | register-fed weights | BN/32 | BK/32 | MODE -- 256 columns forward, 128 in the gradient
+    (none of these launches has the 512 blocks of 256 columns the wide gradient tile asks for)"""
+    breg = 0 if flags & 512 else 0x1000
+    return 0x43540000 | breg | 8 << 8 | (1 if flags & 512 else 2) << 4, 0x43540000 | breg | 4 << 8 | 2 << 4 | 1
+
+
+@pytest.mark.parametrize("n,G,ci,co,h,w,flags", CONVT_BATCHED_CASES,
+                         ids=["-".join(str(v) for v in (c[:6] if c[6] == 0 else c)) for c in CONVT_BATCHED_CASES])
+def test_convT_bf16_batched_passes_exact(n, G, ci, co, h, w, flags):
     """ConvTranspose forward with per-pass BatchNorm constants on its source (the producer's raw output), its input gradient and
-    its weight gradient over the batched passes; outputs between sentinel zones; the kernel family each launch ran is asserted."""
-    flags = 0
+    its weight gradient over the batched passes; outputs between sentinel zones; the build each launch ran is asserted."""
     l = L()
     lib = l.lib()
     g = torch.Generator().manual_seed(77 + ci + h)
@@ -391,7 +405,7 @@ def test_convT_bf16_batched_passes_exact(n, G, ci, co, h, w):
         vd = lib.ustrun_debug_last_conv_variant()
     finally:
         lib.ustrun_debug_flags(old_flags)
-    assert (vf >> 16) == 0x4354 and (vd >> 16) == 0x4354, (hex(vf), hex(vd))
+    assert (vf, vd) == convT_batched_variants(flags), (hex(vf), hex(vd))
     assert rel(from_nhwc(u.float()), r16(ref.detach())) < 1e-6
     assert rel(from_nhwc(da.float()), r16(ar.grad)) < 1e-6
     for b_ in (ubuf, dbuf):
@@ -418,6 +432,8 @@ CONVT_WGRAD_CASES = [
     ("t128_w144_tail", 1, 128, 64, 9, 144, 1, True, 0, 0x54320080),
     ("t128_w256", 2, 128, 64, 64, 256, 2, True, 0, 0x54320080),
     ("old_forced", 4, 256, 128, 16, 16, 2, True, 1 << 27, 0x54310000),
+    ("old_w7", 2, 128, 64, 5, 7, 1, True, 0, 0x54310000),              # the round-1 kernel on its production routes: rows under 16 pixels,
+    ("old_co96", 2, 128, 96, 16, 16, 2, True, 0, 0x54310000),          # ... and column tiles of 32 co
 ]
 
 

@@ -201,9 +201,7 @@ __global__ __launch_bounds__(256, 4) void conv_first_fwd_mfma_kernel(const float
                     s1[n] += v; s2[n] += v * v;
                 }
             }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int idx = lane + 64 * t, row = idx >> 3, ch = idx & 7;
@@ -211,9 +209,7 @@ __global__ __launch_bounds__(256, 4) void conv_first_fwd_mfma_kernel(const float
             const int ox = x0 + row;
             if (oy < H && ox < W) *(bf16x8*)(y + (((long)img * H + oy) * W + ox) * 64 + ch * 8) = v8;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
     if (stat) {
 #pragma unroll
@@ -694,9 +690,7 @@ __global__ __launch_bounds__(256, 3) void conv_first_fwd_stream_kernel(const flo
                     for (int q = 0; q < 4; ++q) h4[q] = (elt_t)acc[n][4 * g + q];
                     *(bf16x4*)(ep + l31 * SPITCH + (n * 32 + 8 * g + 4 * lh) * 2) = h4;
                 }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             const bool rowok = oy < r1;                    // (uniform)
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
@@ -717,9 +711,7 @@ __global__ __launch_bounds__(256, 3) void conv_first_fwd_stream_kernel(const flo
                     }
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
         }
     };
     for (int s = 0; s < nsteps; s += 2) {

@@ -745,9 +745,7 @@ __global__ __launch_bounds__(256, (TH * TW * BN >= 512 * 64 && BN == 64 ? 1 : 2)
         else if (full) park(i, std::false_type{}, std::true_type{});
         else park(i, std::true_type{}, std::true_type{});
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         if (full && n0 + wn * 64 + 64 <= a.C0) {
             // interior tile, one destination (wave-uniform): four plain stores off one base -- the general path below costs
             // three nested exec-mask regions and a 64-bit address chain per store
@@ -790,9 +788,7 @@ __global__ __launch_bounds__(256, (TH * TW * BN >= 512 * 64 && BN == 64 ? 1 : 2)
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
     float s1[2] = {s1v[0][0] + s1v[0][1], s1v[1][0] + s1v[1][1]}, s2[2] = {s2v[0][0] + s2v[0][1], s2v[1][0] + s2v[1][1]};
     if (a.stat) {

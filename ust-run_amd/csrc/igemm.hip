@@ -14,6 +14,7 @@
 // stages of 32 channels: global -> registers (prefetched under the previous stage's MFMAs) ->
 // transform -> LDS (A stored k-major so that lanes read consecutive pixels, B row-major) -> MFMA.
 #include "igemm_tile.h"
+#include "convT_plan.h"
 #include <stdlib.h>
 
 namespace ustrun {
@@ -148,6 +149,7 @@ int igemm_stat_rows_used(const IgemmArgs& a, int dtype) {
     if (dtype == USTRUN_D16 && !(g_debug_flags & 1) && ws64_supported(a)) return ws64_stat_rows(a);
     if (dtype == USTRUN_D16 && halo_supported(a)) return halo_stat_rows_used(a);
     if (dtype == USTRUN_F32X3 && conv3x3_x3_supported(a)) return conv3x3_x3_stat_rows(a);
+    if (const ConvTPlan tp = convT_plan(a, g_debug_flags); dtype == USTRUN_D16 && tp.kind != CONVT_NONE) return tp.stat_rows;
     return cdiv(a.M, 128);
 }
 
@@ -175,14 +177,12 @@ int igemm_launch(const IgemmArgs& a, int dtype, hipStream_t st) {
     for (int i = 0; i < a.nsrc; ++i) grouped |= a.src[i].gN > 0;
     USTRUN_CHECK(!grouped || dtype == USTRUN_D16 || (dtype == USTRUN_F32X3 && conv3x3_x3_supported(a)),
                  "igemm: batched passes reached a kernel without per-pass BatchNorm constants");
-    if (dtype == USTRUN_D16 && (a.join_add || a.join_ref || (a.bny && conv1x1_join_supported(a) && a.nseg == 1 && a.s_in == 1))) {
-        rc = conv1x1_join_launch_bf16(a, st);
-    } else if (dtype == USTRUN_D16) {
-        if (!(g_debug_flags & 1) && ws64_supported(a)) rc = conv3x3_ws64_launch_bf16(a, st);
+    if (dtype == USTRUN_D16) {
+        const ConvTPlan tp = convT_plan(a, g_debug_flags);      // the pixel-linear GEMM family (convT_plan.h): asked once
+        if ((a.join_add || a.join_ref) && !tp.join) { set_error("conv1x1_join: unsupported shape"); rc = 1; }
+        else if (!(g_debug_flags & 1) && ws64_supported(a)) rc = conv3x3_ws64_launch_bf16(a, st);
         else if (halo_supported(a)) rc = conv3x3_halo_launch_bf16(a, st);
-        else if (convT_fwd_supported(a)) rc = convT_fwd_launch_bf16(a, st);
-        else if (conv1x1_supported(a)) rc = conv1x1_launch_bf16(a, st);
-        else if (convT_dgrad_supported(a)) rc = convT_dgrad_launch_bf16(a, st);
+        else if (tp.kind != CONVT_NONE) rc = convT_launch_bf16(a, tp, st);
         else if (grouped) { set_error("igemm: batched passes reached a kernel without per-pass BatchNorm constants"); rc = 1; }
         else rc = igemm_launch_bf16(a, st);
     } else if (dtype == USTRUN_F32X3 && igemm_x3_supported(a) && (!grouped || conv3x3_x3_supported(a))) {     // three-term bf16 products (x3.hip)

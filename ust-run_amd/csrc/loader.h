@@ -76,6 +76,17 @@ __device__ __forceinline__ f32x4 relu4(f32x4 v) {
     v[0] = relu1(v[0]); v[1] = relu1(v[1]); v[2] = relu1(v[2]); v[3] = relu1(v[3]);
     return v;
 }
+// 8 stored values -> BatchNorm affine in f32 (+ ReLU) -> rounded to the storage type: the activation on load of the pixel-linear GEMMs
+// (convT_bf16.hip, the round-1 kernel of wgradT_bf16.hip).  ONE function: the compiler decides contraction once for both
+__device__ __forceinline__ bf16x8 affine8(bf16x8 r, f32x4 sc0, f32x4 sc1, f32x4 sh0, f32x4 sh1, bool relu) {
+    f32x4 lo = (f32x4){(float)r[0], (float)r[1], (float)r[2], (float)r[3]} * sc0 + sh0;
+    f32x4 hi = (f32x4){(float)r[4], (float)r[5], (float)r[6], (float)r[7]} * sc1 + sh1;
+    if (relu) { lo = relu4(lo); hi = relu4(hi); }
+    bf16x8 h;
+    h[0] = (elt_t)lo[0]; h[1] = (elt_t)lo[1]; h[2] = (elt_t)lo[2]; h[3] = (elt_t)lo[3];
+    h[4] = (elt_t)hi[0]; h[5] = (elt_t)hi[1]; h[6] = (elt_t)hi[2]; h[7] = (elt_t)hi[3];
+    return h;
+}
 __device__ __forceinline__ f32x4 max4(f32x4 a, f32x4 b) {
     a[0] = fmaxf(a[0], b[0]); a[1] = fmaxf(a[1], b[1]); a[2] = fmaxf(a[2], b[2]); a[3] = fmaxf(a[3], b[3]);
     return a;

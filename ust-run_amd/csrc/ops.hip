@@ -2,6 +2,7 @@
 // implicit-GEMM / weight-gradient kernels, plus the weight packing kernels.
 #include "common.h"
 #include "loader.h"
+#include "convT_plan.h"
 #include "conv_first_plan.h"
 #include <stdlib.h>
 
@@ -343,7 +344,7 @@ extern "C" int ustrun_convT2x2_fwd(const ustrun_src_t* src, const void* w_fwd, c
         int gN = 0;
         const int G = src_groups(src, 1, N, &gN);
         USTRUN_CHECK(G >= 1, "convT2x2_fwd: inconsistent pass groups");
-        if (G > 1 && !(dtype == USTRUN_D16 && convT_fwd_supported(a))) {
+        if (G > 1 && !(dtype == USTRUN_D16 && convT_plan(a, g_debug_flags).kind == CONVT_FWD)) {
             for (int g = 0; g < G; ++g) {
                 const ustrun_src_t sl = src_slice(*src, g, gN, dtype);
                 USTRUN_TRY(ustrun_convT2x2_fwd(&sl, w_fwd, bias, pass_images(g, gN, N), H, W, Cout,
@@ -391,8 +392,9 @@ extern "C" int ustrun_convT2x2_dgrad_bnsum(const void* du, const void* w_dgrad, 
     a.nz = 1; a.s_out = 1;
     a.out0 = (float*)da; a.C0 = Cin; a.Ho = H; a.Wo = W; a.out_esz = 2;
     a.bny = y; a.bnsc = scale; a.bnsh = shift; a.bn_gN = gN; a.bn_gstride = (long)gstride; a.stat = stat;
-    if (!convT_dgrad_bnsum_supported(a)) return 0;
-    const int used = cdiv(a.M, 128);
+    const ConvTPlan tp = convT_plan(a, g_debug_flags);
+    if (tp.kind != CONVT_DGRAD || !tp.bns_ok) return 0;
+    const int used = tp.stat_rows;
     USTRUN_TRY(check_stat_rows(used, N, H, W, Cin, "convT2x2_dgrad_bnsum"));
     USTRUN_TRY(igemm_launch(a, dtype, (hipStream_t)s));
     *stat_rows = used;
@@ -423,15 +425,7 @@ extern "C" int64_t ustrun_wgrad_partials_bytes(int nseg, int Cin, int Cout, int6
         const int kx = (int)((256 + pairs - 1) / pairs);
         if (kx > slabs) slabs = kx;
     }
-    if (nseg == 4 && Cin % 128 == 0 && Cout % 32 == 0) {         // the ConvTranspose all-taps bf16 kernels
-        int kt; long ct;
-        wgradT_plan(Cin, Cout, npix, &kt, &ct);
-        if (kt > slabs) slabs = kt;
-        if (Cout % 64 == 0) {
-            wgradT2_plan(Cin, Cout, npix, &kt, &ct);
-            if (kt > slabs) slabs = kt;
-        }
-    }
+    if (const int kt = nseg == 4 ? wgradT_max_ksplit(Cin, Cout, npix) : 0; kt > slabs) slabs = kt;      // the ConvTranspose all-taps bf16 kernels (convT_plan.h)
     int64_t b = (int64_t)slabs * nseg * Cin * Cout * sizeof(float);
     if (nseg == 4) b += (int64_t)slabs * Cout * sizeof(float);    // bias column sums ride behind the slabs
     if (nseg == 9 && Cin <= 4 && Cout == 64 && conv_first_wgrad_partials_bytes() > b) b = conv_first_wgrad_partials_bytes();
@@ -554,7 +548,7 @@ extern "C" int ustrun_convT2x2_wgrad(const ustrun_src_t* src, const void* du, in
         int gN = 0;
         const int G = src_groups(src, 1, N, &gN);
         USTRUN_CHECK(G >= 1, "convT2x2_wgrad: inconsistent pass groups");
-        if (G > 1 && !(dtype == USTRUN_D16 && wgradT_supported(a))) {
+        if (G > 1 && !(dtype == USTRUN_D16 && wgradT_plan(a, g_debug_flags).ok)) {
             for (int g = 0; g < G; ++g) {
                 const ustrun_src_t sl = src_slice(*src, g, gN, dtype);
                 USTRUN_TRY(ustrun_convT2x2_wgrad(&sl, (const char*)du + (int64_t)g * gN * 4 * H * W * Cout * act_esz(dtype),
@@ -563,14 +557,13 @@ extern "C" int ustrun_convT2x2_wgrad(const ustrun_src_t* src, const void* du, in
             return 0;
         }
     }
-    if (dtype == USTRUN_D16 && wgradT_supported(a)) {       // all four taps (and the bias) in one GEMM: wgradT_bf16.hip
-        wgradT_plan_for(a, &a.ksplit, &a.kchunk);
-        slabs = a.ksplit;
+    if (const WgradTPlan tp = wgradT_plan(a, g_debug_flags); dtype == USTRUN_D16 && tp.ok) {       // all four taps (and the bias) in one GEMM: wgradT_bf16.hip
+        a.ksplit = slabs = tp.ksplit; a.kchunk = tp.kchunk;
         const int64_t slab_bytes = (int64_t)slabs * 4 * a.Cin * Cout * 4;
         USTRUN_CHECK(partials_bytes >= slab_bytes + (db ? (int64_t)slabs * Cout * 4 : 0), "convT2x2_wgrad: partials too small");
         a.bias_partials = db ? partials + slab_bytes / 4 : nullptr;
         prof_begin(1, 2.0 * a.M * 4 * a.Cin * Cout, 2.0 * (a.M * (double)a.Cin + 4.0 * a.M * Cout) + 16.0 * a.Cin * Cout, (hipStream_t)s);
-        const int rc = wgradT_launch_bf16(a, (hipStream_t)s);
+        const int rc = wgradT_launch_bf16(a, tp, (hipStream_t)s);
         prof_end((hipStream_t)s);
         USTRUN_TRY(rc);
         if (db) USTRUN_TRY(reduce_rows(a.bias_partials, slabs, Cout, 0, Cout, db, accumulate, (hipStream_t)s));

@@ -8,6 +8,7 @@
 // shifted-add adjoints).
 #include "common.h"
 #include "loader.h"
+#include "convT_plan.h"
 
 namespace ustrun {
 namespace {
@@ -371,11 +372,12 @@ extern "C" int ustrun_conv1x1_dgrad_join(const void* dy, const void* w_dgrad, in
     a.s_in = 1; a.nseg = 1; a.segw = 1; a.d0 = 0; a.dstep = 1;
     a.nz = 1; a.s_out = 1;
     a.out0 = (float*)g; a.C0 = Cin; a.Ho = H; a.Wo = W; a.out_esz = 2;
-    if (!conv1x1_join_supported(a)) return 0;
+    const ConvTPlan tp = convT_plan(a, g_debug_flags);
+    if (!tp.join_ok) return 0;
     a.join_add = add; a.join_ref = ref;
     if (y) {
         a.bny = y; a.bnsc = scale; a.bnsh = shift; a.stat = stat;
-        const int used = cdiv(a.M, 128);
+        const int used = tp.stat_rows;
         USTRUN_TRY(stat_rows_within_bound(used, N, H, W, Cin, "conv1x1_dgrad_join"));
         *stat_rows = used;
     }

@@ -15,12 +15,59 @@
 #include "common.h"
 #include "loader.h"
 #include "tn_gemm.h"
+#include "convT_plan.h"
 
 namespace ustrun {
 namespace {
 
-constexpr int TM = 128, TN = 128, KP = 64, RB = 256;   // tile, pixels per stage, LDS row pitch (bytes)
+constexpr int TM = WGT_TM, KP = WGT_KP, RB = WGT_RB;   // round 1: ci tile, pixels per stage, LDS row pitch (bytes)
 
+// ---- what the two kernels share.  The block's place: grid = ci tiles * column tiles * ksplit in XCD order, slice-major -- all (ci, column)
+// tiles of one pixel slice share one XCD's L2 (the kernels are HBM-bound: 5.7 TB/s measured) ----
+struct WgtBlock { int ks, mtile, ntile; long kbeg, kend; };
+__device__ __forceinline__ WgtBlock wgt_block(const WgradArgs& a, int ntn) {
+    const int nblk = gridDim.x, tiles = nblk / a.ksplit;
+    const int lin = xcd_linear(blockIdx.x, nblk);
+    WgtBlock b;
+    b.ks = lin / tiles;
+    const int tile = lin - b.ks * tiles;
+    b.mtile = tile / ntn; b.ntile = tile % ntn;
+    b.kbeg = (long)b.ks * a.kchunk;
+    b.kend = (b.kbeg + a.kchunk < a.M) ? b.kbeg + a.kchunk : a.M;
+    return b;
+}
+// The BatchNorm constants of a thread's 8-channel group, reloaded when the pixels enter another pass (a stage never straddles two: the plan checks)
+struct PassConsts {
+    f32x4 sc0 = {1.f, 1.f, 1.f, 1.f}, sc1 = sc0, sh0 = {0.f, 0.f, 0.f, 0.f}, sh1 = sh0;
+    int cur_grp = -1;
+    // PIN: the loads complete HERE, inside the rare branch: left pending, hipcc puts `s_waitcnt vmcnt(0)` in front of their first use -- the
+    // activation of every stage -- and that drains the transfers the round-5 kernel keeps two stages in flight
+    template <bool PIN> __device__ __forceinline__ void load(const SrcDev& S, long gpix, long k0, int ch) {
+        const int grp = gpix > 0 ? (int)(k0 / gpix) : 0;
+        if (S.scale != nullptr && grp != cur_grp) {
+            const long o = (long)grp * (gpix > 0 ? S.gstride : 0) + ch;
+            sc0 = *(const f32x4*)(S.scale + o); sc1 = *(const f32x4*)(S.scale + o + 4);
+            sh0 = *(const f32x4*)(S.shift + o); sh1 = *(const f32x4*)(S.shift + o + 4);
+            if constexpr (PIN) asm volatile("" : "+v"(sc0), "+v"(sc1), "+v"(sh0), "+v"(sh1));
+            cur_grp = grp;
+        }
+    }
+};
+// The slab in the torch layout [Cin][Cout][2][2], one 32-ci accumulator of one 8-co group: rows of D are ci (registers, from ci on); lane
+// 16 g + 4 tap + c is column (co8 + 4 g + c, tap) -> the 32 lanes of a row write 32 consecutive floats.  (The accumulator by value: handed
+// over as part of the kernel's array, the round-5 kernel spilled.)
+__device__ __forceinline__ int wgt_lane_co(int lane) { return 4 * ((lane & 31) >> 4) + (lane & 3); }
+__device__ __forceinline__ void wgt_store_slab(float* slab, int Cout, int ci, int co, int lane, f32x16 v) {
+    float* o = slab + ((long)(ci + 4 * (lane >> 5)) * Cout + co) * 4 + ((lane >> 2) & 3);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[(long)((r & 3) + 8 * (r >> 2)) * Cout * 4] = v[r];
+}
+// The bias gradient of column co: v = the lane's column sum; fold the four taps (lane bits 2..3), one lane per column writes
+__device__ __forceinline__ void wgt_fold_bias(float v, float* row, int co, int lane) {
+    v += __shfl_xor(v, 4);
+    v += __shfl_xor(v, 8);
+    if ((lane >> 5) == 0 && ((lane >> 2) & 3) == 0) row[co] = v;
+}
 // du fragment of 8-co group t: lane (q, p, g) reads row q, tap p, channels 8t + 4g .. +3 of the [tap][32 co] row,
 // so after the transpose lane 16g + 4*tap + c of the MFMA holds column (co = 8t + 4g + c, tap)
 __device__ __forceinline__ bf16x8 tr_frag_du(const char* tile, int k0, int t, int lane) {
@@ -30,23 +77,17 @@ __device__ __forceinline__ bf16x8 tr_frag_du(const char* tile, int k0, int t, in
     return tr_pair(tile + r0 * RB + off, tile + r1 * RB + off);
 }
 
-// grid = (ci tiles * column tiles, ksplit)
 __global__ __launch_bounds__(256, 2) void wgradT_bf16_kernel(const WgradArgs a, const int ntn) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* As = smem;                      // 2 x [KP][TM] bf16
-    char* Bs = smem + 2 * KP * RB;        // 2 x [KP][TN] bf16
+    char* Bs = smem + 2 * KP * RB;        // 2 x [KP][4 taps x 32 co] bf16
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform: LDS-DMA bases and role tests stay scalar
     const int wm = wave >> 1, wn = wave & 1;
-    // XCD order: all (ci, column) tiles of one pixel slice share one XCD's L2 (the kernel is HBM-bound: 5.7 TB/s measured)
-    const int nblk = gridDim.x, tiles = nblk / a.ksplit;
-    const int lin = xcd_linear(blockIdx.x, nblk);
-    const int ks = lin / tiles, tile = lin - ks * tiles;
-    const int mtile = tile / ntn, ntile = tile % ntn;
-    const int ci0 = mtile * TM, co0 = ntile * 32;
-    const long kbeg = (long)ks * a.kchunk;
-    const long kend = (kbeg + a.kchunk < a.M) ? kbeg + a.kchunk : a.M;
+    const WgtBlock blk = wgt_block(a, ntn);
+    const int ks = blk.ks, mtile = blk.mtile, ci0 = mtile * TM, co0 = blk.ntile * 32;
+    const long kbeg = blk.kbeg, kend = blk.kend;
     const int W = a.Wb;
     const float invW = 1.f / (float)W;
 
@@ -55,23 +96,13 @@ __global__ __launch_bounds__(256, 2) void wgradT_bf16_kernel(const WgradArgs a, 
     const int c8 = tid & 15;
     const int cl = ci0 + 8 * c8;
     const bool aff = S.scale != nullptr;
-    f32x4 asc0 = {1.f, 1.f, 1.f, 1.f}, asc1 = asc0, ash0 = {0.f, 0.f, 0.f, 0.f}, ash1 = ash0;
-    int cur_grp = -1;                     // batched passes: a 64-pixel stage never straddles two passes (host check)
+    PassConsts pc;
     const long gpix = S.gN > 0 ? (long)S.gN * a.Hb * a.Wb : 0;
-    auto load_consts = [&](long k0) {
-        const int grp = gpix > 0 ? (int)(k0 / gpix) : 0;
-        if (aff && grp != cur_grp) {
-            const long o = (long)grp * (gpix > 0 ? S.gstride : 0) + cl;
-            asc0 = *(const f32x4*)(S.scale + o); asc1 = *(const f32x4*)(S.scale + o + 4);
-            ash0 = *(const f32x4*)(S.shift + o); ash1 = *(const f32x4*)(S.shift + o + 4);
-            cur_grp = grp;
-        }
-    };
     const elt_t* sp = (const elt_t*)S.ptr + cl;
     const int arow = tid >> 4;
     bf16x8 av[4];
     auto load_A = [&](long k0) {
-        load_consts(k0);                  // write_A of this stage runs before the next load_A
+        pc.load<false>(S, gpix, k0, cl);  // write_A of this stage runs before the next load_A
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const long m = k0 + arow + 16 * i;
@@ -85,13 +116,7 @@ __global__ __launch_bounds__(256, 2) void wgradT_bf16_kernel(const WgradArgs a, 
         for (int i = 0; i < 4; ++i) {
             const int row = arow + 16 * i;
             bf16x8 h = av[i];
-            if (aff && k0 + row < kend) {       // rows past the range stay zero
-                f32x4 lo = (f32x4){(float)h[0], (float)h[1], (float)h[2], (float)h[3]} * asc0 + ash0;
-                f32x4 hi = (f32x4){(float)h[4], (float)h[5], (float)h[6], (float)h[7]} * asc1 + ash1;
-                if (S.relu) { lo = relu4(lo); hi = relu4(hi); }
-                h[0] = (elt_t)lo[0]; h[1] = (elt_t)lo[1]; h[2] = (elt_t)lo[2]; h[3] = (elt_t)lo[3];
-                h[4] = (elt_t)hi[0]; h[5] = (elt_t)hi[1]; h[6] = (elt_t)hi[2]; h[7] = (elt_t)hi[3];
-            }
+            if (aff && k0 + row < kend) h = affine8(h, pc.sc0, pc.sc1, pc.sh0, pc.sh1, S.relu);      // rows past the range stay zero
             *(bf16x8*)(dst + row * RB + ((c8 * 16) ^ ((row & 3) << 6))) = h;
         }
     };
@@ -128,9 +153,7 @@ __global__ __launch_bounds__(256, 2) void wgradT_bf16_kernel(const WgradArgs a, 
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     const bool do_bias = a.bias_partials != nullptr && mtile == 0 && wm == 0;      // wave-uniform
     f32x16 accb[2];
-    bf16x8 ones;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) ones[q] = (elt_t)1.f;
+    const bf16x8 ones = {(elt_t)1.f, (elt_t)1.f, (elt_t)1.f, (elt_t)1.f, (elt_t)1.f, (elt_t)1.f, (elt_t)1.f, (elt_t)1.f};
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -180,28 +203,13 @@ __global__ __launch_bounds__(256, 2) void wgradT_bf16_kernel(const WgradArgs a, 
         buf ^= 1;
     }
 
-    // slab in the torch layout [Cin][Cout][2][2]: rows of D are ci (registers); lane 16g + 4*tap + c is column
-    // (co = co0 + 8t + 4g + c, tap) -> the 32 lanes of a row write 32 consecutive floats
     float* slab = a.partials + (long)ks * 4 * a.Cin * a.Cout;
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int lg = l31 >> 4, ltap = (l31 >> 2) & 3, lc = l31 & 3;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const int co = co0 + 8 * (2 * wn + j) + 4 * lg + lc;
-        float* o = slab + (long)co * 4 + ltap;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int ci = ci0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                o[(long)ci * a.Cout * 4] = acc[i][j][r];
-            }
-        if (do_bias) {      // every row of accb is the column sum; fold the four taps (lane bits 2..3)
-            float v = accb[j][0];
-            v += __shfl_xor(v, 4);
-            v += __shfl_xor(v, 8);
-            if (lh == 0 && ltap == 0) a.bias_partials[(long)ks * a.Cout + co] = v;
-        }
+        const int co = co0 + 8 * (2 * wn + j) + wgt_lane_co(lane);
+        wgt_store_slab(slab, a.Cout, ci0 + wm * 64, co, lane, acc[0][j]);
+        wgt_store_slab(slab, a.Cout, ci0 + wm * 64 + 32, co, lane, acc[1][j]);
+        if (do_bias) wgt_fold_bias(accb[j][0], a.bias_partials + (long)ks * a.Cout, co, lane);      // every row of accb is the column sum
     }
 }
 
@@ -223,7 +231,6 @@ __global__ __launch_bounds__(256, 2) void wgradT_bf16_kernel(const WgradArgs a, 
 //    and come back as zeros;
 //  * the bottom of stage s waits with a COUNTED vmcnt for stage s + 1, applies BatchNorm + ReLU to it IN PLACE (a thread's items
 //    always hold one channel group: its constants stay in registers), one barrier per stage.
-constexpr int KP2 = 32, BRB2 = 512;
 // the bias gradient = column sums of du: each lane adds the eight K entries of its column with four packed dot products against
 // (1, 1) -- four registers and 16 VALU instructions per 16 pixels where an all-ones MFMA per fragment took 64 registers
 #ifdef USTRUN_ELT_F16
@@ -231,16 +238,7 @@ constexpr int KP2 = 32, BRB2 = 512;
 #else
 #define USTRUN_DOT2_ONES(pair, acc) __builtin_amdgcn_fdot2_f32_bf16(pair, (bf16x2){(elt_t)1.f, (elt_t)1.f}, acc, false)
 #endif
-template <int TM> struct T2 {
-    static constexpr int ARB = TM * 2;                       // activation row pitch (bytes)
-    static constexpr int ATILE = KP2 * ARB, BTILE = KP2 * BRB2, STAGE = ATILE + BTILE;
-    static constexpr int NTH = 2 * TM;                       // threads: 512 / 256
-    static constexpr int AIT = KP2 * (TM / 8) / NTH;         // 16-byte activation items per thread and stage: 2
-    static constexpr int BIT = KP2 * 32 / NTH;               // du items: 2 / 4
-    static constexpr int WM = TM / 64, WN = 2;               // waves along ci / along the columns (one 32-co half each)
-    static constexpr int NT = 4;                             // du fragments (8 co x 4 taps each) per wave
-};
-
+// (T2<TM>, the tile geometry: convT_plan.h)
 // DIAG (a development build, launched only while ustrun_debug_buffer is set; tools/diag_wgradT.py): phase stamps per wave into
 // dbg[block][wave 0..7][8] -- cycles (s_memtime) summed over the stages: 0 issuing the transfers two stages ahead, 1 fragment reads +
 // MFMAs, 2 the counted wait for the next stage, 3 its activation in place, 4 the barrier; 5 = stages.  Measured (1024 -> 512 at 16 x
@@ -263,13 +261,9 @@ __global__ __launch_bounds__(2 * TM, 2) void wgradT2_bf16_kernel(const WgradArgs
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    const int nblk = gridDim.x, tiles = nblk / a.ksplit;          // XCD-contiguous (slice-major) order, as above
-    const int lin = xcd_linear(blockIdx.x, nblk);
-    const int ks = lin / tiles, tile = lin - ks * tiles;
-    const int mtile = tile / ntn, ntile = tile % ntn;
-    const int ci0 = mtile * TM, co0 = ntile * 64;
-    const long kbeg = (long)ks * a.kchunk;
-    const long kend = (kbeg + a.kchunk < a.M) ? kbeg + a.kchunk : a.M;
+    const WgtBlock blk = wgt_block(a, ntn);
+    const int ks = blk.ks, mtile = blk.mtile, ci0 = mtile * TM, co0 = blk.ntile * 64;
+    const long kbeg = blk.kbeg, kend = blk.kend;
     const int W = a.Wb;
 
     // ---- this thread's transfer items (tile-invariant): linear 16-byte slot L = tid + NTH i of the stage's A / du tile ----
@@ -296,21 +290,9 @@ __global__ __launch_bounds__(2 * TM, 2) void wgradT2_bf16_kernel(const WgradArgs
         boff[i] = (2 * row + (tap >> 1) * 2 * W + (tap & 1)) * P + (co0 + 32 * half + 8 * cg) * 2;
     }
     const int wrapB = 2 * W * P;                                  // one more image row wrapped: + 2 W hi-resolution pixels
-    f32x4 asc0 = {1.f, 1.f, 1.f, 1.f}, asc1 = asc0, ash0 = {0.f, 0.f, 0.f, 0.f}, ash1 = ash0;
-    int cur_grp = -1;
+    PassConsts pc;
     const long gpix = S.gN > 0 ? (long)S.gN * a.Hb * a.Wb : 0;
-    auto load_consts = [&](long k0) {
-        const int grp = gpix > 0 ? (int)(k0 / gpix) : 0;
-        if (aff && grp != cur_grp) {
-            const long o = (long)grp * (gpix > 0 ? S.gstride : 0) + ci0 + 8 * acg;
-            asc0 = *(const f32x4*)(S.scale + o); asc1 = *(const f32x4*)(S.scale + o + 4);
-            ash0 = *(const f32x4*)(S.shift + o); ash1 = *(const f32x4*)(S.shift + o + 4);
-            // the loads complete HERE, inside the rare branch: left pending, hipcc puts `s_waitcnt vmcnt(0)` in front of their first
-            // use -- the activation of every stage -- and that drains the transfers this kernel keeps two stages in flight
-            asm volatile("" : "+v"(asc0), "+v"(asc1), "+v"(ash0), "+v"(ash1));
-            cur_grp = grp;
-        }
-    };
+    auto load_consts = [&](long k0) { pc.load<true>(S, gpix, k0, ci0 + 8 * acg); };
     const char* const sbytes = (const char*)S.ptr;
     const char* const dbytes = (const char*)a.dy;
     const long sW2 = (long)S.sW * 2;
@@ -345,7 +327,7 @@ __global__ __launch_bounds__(2 * TM, 2) void wgradT2_bf16_kernel(const WgradArgs
 #pragma unroll
         for (int i = 0; i < AIT; ++i) {
             u32x4* cell = (u32x4*)(stage + (tid + NTH * i) * 16);
-            u32x4 u = act8_bf16(*cell, asc0, asc1, ash0, ash1, S.relu ? (short)0 : (short)0x8000);
+            u32x4 u = act8_bf16(*cell, pc.sc0, pc.sc1, pc.sh0, pc.sh1, S.relu ? (short)0 : (short)0x8000);
             if (arow[i] >= rem) u = (u32x4){0u, 0u, 0u, 0u};
             *cell = u;
         }
@@ -436,117 +418,41 @@ __global__ __launch_bounds__(2 * TM, 2) void wgradT2_bf16_kernel(const WgradArgs
             for (int k = 0; k < 8; ++k) dbg[((long)blockIdx.x * 8 + wave) * 8 + k] = k < 5 ? dsum[k] : (k == 5 ? (unsigned long long)nstage : 0ull);
     }
 
-    // slab in the torch layout [Cin][Cout][2][2]: rows of D are ci (registers); lane 16 g + 4 tap + c is column (co, tap)
     float* slab = a.partials + (long)ks * 4 * a.Cin * a.Cout;
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int lg = l31 >> 4, ltap = (l31 >> 2) & 3, lc = l31 & 3;
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
-        const int co = co0 + 32 * half + 8 * (t0 + j) + 4 * lg + lc;
-        float* o = slab + (long)co * 4 + ltap;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int ci = ci0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                o[(long)ci * a.Cout * 4] = acc[i][j][r];
-            }
-        if (do_bias) {      // lane l holds the sum of its column over K entries 8 (l >> 5) .. + 7 of every 16: fold the halves, then the four taps
-            float v = accb[j];
-            v += __shfl_xor(v, 32);
-            v += __shfl_xor(v, 4);
-            v += __shfl_xor(v, 8);
-            if (lh == 0 && ltap == 0) a.bias_partials[(long)ks * a.Cout + co] = v;
-        }
+        const int co = co0 + 32 * half + 8 * (t0 + j) + wgt_lane_co(lane);
+        wgt_store_slab(slab, a.Cout, ci0 + wm * 64, co, lane, acc[0][j]);
+        wgt_store_slab(slab, a.Cout, ci0 + wm * 64 + 32, co, lane, acc[1][j]);
+        // lane l holds the sum of its column over K entries 8 (l >> 5) .. + 7 of every 16: fold the halves first
+        if (do_bias) wgt_fold_bias(accb[j] + __shfl_xor(accb[j], 32), a.bias_partials + (long)ks * a.Cout, co, lane);
     }
 }
 
 }  // namespace
 
-static bool wgradT_base_ok(const WgradArgs& a) {
-    if (a.nseg != 4 || a.segw != 2 || a.dy_s != 2 || a.astep != 0 || a.d0 != 0 || a.ashift != 0 || a.dy_esz != 2 || a.nsrc != 1) return false;
-    const SrcDev& s = a.src[0];
-    if (s.esz != 2 || s.sC != 1 || s.pool || s.off_y || s.off_x || s.LH != a.Hb || s.LW != a.Wb) return false;
-    if ((s.relu && !s.scale) || (s.sW & 7)) return false;
-    if (s.sH != (long)a.Wb * s.sW || s.sN != (long)a.Hb * s.sH) return false;      // pixel-linear source
-    if (a.dyH != 2 * a.Hb || a.dyW != 2 * a.Wb || a.Wb >= 32768) return false;
-    return true;
-}
-
-// the round-5 kernel: whole 64-co column tiles, 128 / 256-ci row tiles, rows of >= 16 pixels (a 32-pixel stage wraps at most two
-// image rows), 32-bit item offsets; ustrun_debug_flags bit 27: never (A/B runs against the round-1 kernel)
-static int wgradT2_tm(const WgradArgs& a) {
-    if (!wgradT_base_ok(a) || (g_debug_flags & (1 << 27))) return 0;
-    const SrcDev& s = a.src[0];
-    if (a.Cout % 64 || a.Cin % 128 || a.Wb < 16) return 0;
-    if (s.gN > 0 && ((long)s.gN * a.Hb * a.Wb) % KP2) return 0;         // stages must not straddle passes
-    if ((long)KP2 * s.sW * 2 + (long)a.Cin * 2 >= (1L << 30)) return 0;
-    if ((2L * KP2 + 6L * a.Wb + 2) * a.Cout * 2 >= (1L << 30)) return 0;
-    return a.Cin % 256 == 0 ? 256 : 128;
-}
-
-bool wgradT_supported(const WgradArgs& a) {
-    if (!wgradT_base_ok(a)) return false;
-    if (wgradT2_tm(a)) return true;
-    const SrcDev& s = a.src[0];
-    if (s.gN > 0 && ((long)s.gN * a.Hb * a.Wb) % KP) return false;        // stages must not straddle passes
-    return a.Cin % 128 == 0 && a.Cout % 32 == 0;
-}
-
-// split-K plan: one resident wave of blocks (2 per CU), at least four 64-pixel stages per block
-int wgradT_plan(int Cin, int Cout, long M, int* ksplit, long* kchunk) {
-    const long tiles = (long)(Cin / TM) * (Cout / 32);
-    long ks = (512 + tiles - 1) / tiles;
-    if (ks > M / (4 * KP)) ks = M / (4 * KP);
-    if (ks < 1) ks = 1;
-    long chunk = (M + ks - 1) / ks;
-    chunk = (chunk + KP - 1) / KP * KP;
-    *kchunk = chunk; *ksplit = (int)((M + chunk - 1) / chunk);
+// the round-5 kernel: raise its dynamic-LDS limit, launch
+template <int TM, bool DIAG>
+static int launch_t2(const WgradArgs& a, const WgradTPlan& p, unsigned long long* dbg, hipStream_t st) {
+    USTRUN_TRY(ensure_dynamic_lds((const void*)wgradT2_bf16_kernel<TM, DIAG>, p.lds, "wgradT2_bf16"));
+    hipLaunchKernelGGL((wgradT2_bf16_kernel<TM, DIAG>), dim3(p.grid), dim3(p.threads), p.lds, st, a, a.Cout / p.cols, dbg);
+    USTRUN_LAUNCH_CHECK("wgradT2_bf16");
     return 0;
 }
-// ... of the round-5 kernel: one resident round of blocks (one 256-ci block or two 128-ci blocks per CU), at least eight 32-pixel
-// stages per block.  (Cin, Cout alone decide the tile: the partials bound ustrun_wgrad_partials_bytes publishes takes the larger
-// of the two plans.)
-int wgradT2_plan(int Cin, int Cout, long M, int* ksplit, long* kchunk) {
-    const int tm = Cin % 256 == 0 ? 256 : 128;
-    const long tiles = (long)(Cin / tm) * (Cout / 64);
-    long ks = ((tm == 256 ? 256 : 512) + tiles - 1) / tiles;
-    if (ks > M / (8 * KP2)) ks = M / (8 * KP2);
-    if (ks < 1) ks = 1;
-    long chunk = (M + ks - 1) / ks;
-    chunk = (chunk + KP2 - 1) / KP2 * KP2;
-    *kchunk = chunk; *ksplit = (int)((M + chunk - 1) / chunk);
-    return 0;
-}
-int wgradT_plan_for(const WgradArgs& a, int* ksplit, long* kchunk) {
-    return wgradT2_tm(a) ? wgradT2_plan(a.Cin, a.Cout, a.M, ksplit, kchunk) : wgradT_plan(a.Cin, a.Cout, a.M, ksplit, kchunk);
-}
 
-int wgradT_launch_bf16(const WgradArgs& a, hipStream_t st) {
-    const int tm = wgradT2_tm(a);
-    if (tm) {
-        dim3 grid((a.Cin / tm) * (a.Cout / 64) * a.ksplit), block(2 * tm);
-        set_last_wgrad_variant(0x54320000 | tm);                   // 'T2' | ci tile
-        unsigned long long* dbg = nullptr;
-        USTRUN_TRY(debug_buffer_for((long)grid.x, "wgradT2", &dbg));
-        if (tm == 256 && dbg) {                  // ustrun_debug_buffer set: the stamped build (tools/diag_wgradT.py)
-            USTRUN_TRY(ensure_dynamic_lds((const void*)wgradT2_bf16_kernel<256, true>, 3 * T2<256>::STAGE, "wgradT2_bf16"));
-            hipLaunchKernelGGL((wgradT2_bf16_kernel<256, true>), grid, block, 3 * T2<256>::STAGE, st, a, a.Cout / 64, dbg);
-        } else if (tm == 256) {
-            USTRUN_TRY(ensure_dynamic_lds((const void*)wgradT2_bf16_kernel<256>, 3 * T2<256>::STAGE, "wgradT2_bf16"));
-            hipLaunchKernelGGL((wgradT2_bf16_kernel<256>), grid, block, 3 * T2<256>::STAGE, st, a, a.Cout / 64, (unsigned long long*)nullptr);
-        } else {
-            USTRUN_TRY(ensure_dynamic_lds((const void*)wgradT2_bf16_kernel<128>, 3 * T2<128>::STAGE, "wgradT2_bf16"));
-            hipLaunchKernelGGL((wgradT2_bf16_kernel<128>), grid, block, 3 * T2<128>::STAGE, st, a, a.Cout / 64, (unsigned long long*)nullptr);
-        }
-        USTRUN_LAUNCH_CHECK("wgradT2_bf16");
+// the launch of the kernel wgradT_plan chose (a.ksplit, a.kchunk are the plan's)
+int wgradT_launch_bf16(const WgradArgs& a, const WgradTPlan& p, hipStream_t st) {
+    USTRUN_CHECK(p.ok && a.ksplit == p.ksplit && a.kchunk == p.kchunk, "wgradT: launch without its plan");
+    set_last_wgrad_variant(p.variant);
+    if (p.kernel == 1) {
+        hipLaunchKernelGGL(wgradT_bf16_kernel, dim3(p.grid), dim3(p.threads), p.lds, st, a, a.Cout / p.cols);
+        USTRUN_LAUNCH_CHECK("wgradT_bf16");
         return 0;
     }
-    set_last_wgrad_variant(0x54310000);                            // 'T1'
-    dim3 grid((a.Cin / TM) * (a.Cout / 32) * a.ksplit), block(256);
-    hipLaunchKernelGGL(wgradT_bf16_kernel, grid, block, 4 * KP * RB, st, a, a.Cout / 32);
-    USTRUN_LAUNCH_CHECK("wgradT_bf16");
-    return 0;
+    unsigned long long* dbg = nullptr;
+    USTRUN_TRY(debug_buffer_for((long)p.grid, "wgradT2", &dbg));
+    if (p.tm == 256 && dbg) return launch_t2<256, true>(a, p, dbg, st);      // ustrun_debug_buffer set: the stamped build (tools/diag_wgradT.py)
+    return p.tm == 256 ? launch_t2<256, false>(a, p, nullptr, st) : launch_t2<128, false>(a, p, nullptr, st);
 }
 
 }  // namespace ustrun
