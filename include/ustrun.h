@@ -542,6 +542,49 @@ int64_t ustrun_sdf_from_dist2_work_bytes(int N, int K, int H, int W);
 int ustrun_sdf_from_dist2(const int32_t* s2, const int32_t* flags, int N, int K, int H, int W,
                           void* work, int64_t work_bytes, float* sdf, ustrun_stream_t s);
 
+/* ---- volumes [D][H][W]: the 3-D twins of the three entries above (csrc/edt3d.hip).  compute_sdf is documented for
+ * shape = (batch_size, x, y, z) (utils/util.py:208-217), and the medpy functions of the reference's test() (binary.hd95 / asd,
+ * train.py:306-325) are n-dimensional and take `voxelspacing`.  The metric has three integer axis weights (wz, wy, wx), each in
+ * 1..255:
+ *   d2(p, q) = wz^2 dz^2 + wy^2 dy^2 + wx^2 dx^2        (int32, exact; unit weights: scipy's default)
+ * -- millimetre spacing is mapped onto weights by the host (utils.metrics.spacing_weights), the device never leaves integers.
+ * Every entry refuses, before any launch and before any pointer is used: D, H or W outside 1..1024, D * H * W > 2^27,
+ * N * K > 32767, a weight outside 1..255, and wz^2 (D-1)^2 + wy^2 (H-1)^2 + wx^2 (W-1)^2 > 2^31 - 2 (the largest d2 of the volume
+ * must stay below USTRUN_DIST_NONE); then null pointers, a short work buffer (the *_work_bytes queries: -1 + error for sizes out
+ * of range) and misaligned pointers (work 16-byte, out 8-byte, the rest to their element).  Asynchronous on s, nothing is
+ * allocated, nothing waits for the device; integer atomics and fixed-order f64 sums only: equal bits on every run.
+ *
+ * ustrun_signed_dist2_3d: mask as ustrun_signed_dist2 reads it, with D * H * W voxels where that has H * W pixels.
+ * s2[N*K][D][H][W], int32: + d2 to the nearest foreground voxel at a background voxel, - d2 to the nearest background voxel at a
+ * foreground voxel, over the voxels of the volume only (scipy's convention).  flags[N*K]: 0 = empty, 1 = mixed, 2 = full VOLUME;
+ * a volume without the opposite kind holds + USTRUN_DIST_NONE resp. - USTRUN_DIST_NONE, whatever its single slices hold.
+ *
+ * ustrun_sdf_from_dist2_3d: the normalisation of util.py:231-234 per volume (the maxima are taken over the whole volume), as
+ * ustrun_sdf_from_dist2 per plane; defined for unit weights, where the inner boundary (find_boundaries(mode="inner") in 3-D: a
+ * foreground voxel with a background 6-neighbour inside the volume) is s2 == -1 and is written as exactly 0.0f.
+ *
+ * ustrun_surface_metrics_3d: pred / gt as ustrun_surface_metrics takes them.  border(A) = A & ~erode(A) with the 6-neighbour
+ * cross and background outside the volume (medpy: generate_binary_structure(3, 1), binary_erosion defaults); every border voxel
+ * of one mask gets d2 to the nearest border voxel of the other.  out[n][c] = one USTRUN_SURFACE3D_RECORD_BYTES record:
+ *   int32 |border(P)|, |border(G)|
+ *   int32 d2[k], d2[min(k+1, n-1)]   the order statistics of the union multiset, n = |border(P)| + |border(G)|,
+ *                                    k = floor(0.95 (n-1)) in f64
+ *   int32 max d2 over border(P), max d2 over border(G)
+ *   f64   sum of sqrt(d2) over border(P);   f64 sum of sqrt(d2) over border(G)     (fixed-order sums)
+ * When either border is empty both counts are reported and the rest is 0.                                                   */
+#define USTRUN_SURFACE3D_RECORD_BYTES 40
+int64_t ustrun_signed_dist2_3d_work_bytes(int N, int K, int D, int H, int W);
+int ustrun_signed_dist2_3d(const void* mask, int mask_is_i64, int N, int K, int by_class, int D, int H, int W,
+                           int wz, int wy, int wx, void* work, int64_t work_bytes, int32_t* s2, int32_t* flags,
+                           ustrun_stream_t s);
+int64_t ustrun_sdf_from_dist2_3d_work_bytes(int N, int K, int D, int H, int W);
+int ustrun_sdf_from_dist2_3d(const int32_t* s2, const int32_t* flags, int N, int K, int D, int H, int W,
+                             void* work, int64_t work_bytes, float* sdf, ustrun_stream_t s);
+int64_t ustrun_surface_metrics_3d_work_bytes(int N, int K, int D, int H, int W);
+int ustrun_surface_metrics_3d(const void* pred, const void* gt, int pred_is_i64, int gt_is_i64, int N, int K, int by_class,
+                              int D, int H, int W, int wz, int wy, int wx, void* work, int64_t work_bytes, void* out,
+                              ustrun_stream_t s);
+
 /* ---- SGD(momentum, weight decay) + EMA teacher over flat buffers: train.py:512,848,87-93 ------
  * g += wd*p; v = first ? g : mu*v + g; p -= lr*v; t = alpha*t + (1-alpha)*p                    */
 /* ---- dynamic loss scale of the IEEE-half path: torch.cuda.amp.GradScaler as train.py:552,842-845 uses it, on the device.

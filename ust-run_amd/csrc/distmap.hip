@@ -12,17 +12,16 @@
 //                     outwards from x while (x - x')^2 can still win (exact: what is left out is >= the minimum).  A row whose
 //                     opposite map has no finite entry belongs to a plane without that kind (a pixel of it anywhere in the plane
 //                     would give its column a finite entry in every row): no search, +- USTRUN_DIST_NONE.  Row 0 writes the flag.
-// ustrun_sdf_from_dist2, two launches: the integer maxima of both signs per plane (atomicMax: exact, order-free), then
+// ustrun_sdf_from_dist2, two launches (edt_scan.h: planemax_kernel, normalise_kernel, shared with edt3d.hip): the integer maxima of both signs per plane (atomicMax: exact, order-free), then
 //   sdf = sqrt(neg) / sqrt(maxneg) - sqrt(pos) / sqrt(maxpos) per pixel in f64, rounded to f32 once.
 // No floating-point reduction anywhere: two runs give the same bits.
 #include "common.h"
-#include "edt_scan.h"
+#include "edt_scan.h"        // COL_INF, SURF_MAX, fg_at, colscan_kernel, planemax_kernel, normalise_kernel
 
 namespace ustrun {
 namespace {
 
 constexpr int ROWS_PER_BLOCK = 4;        // signed_row_kernel: one wave per row
-constexpr int MAX_PER_BLOCK = 2048;      // planemax_kernel: pixels per block
 constexpr int64_t MAX_PLANES = 65535 / 2;
 
 static inline int64_t up16(int64_t b) { return (b + 15) & ~(int64_t)15; }
@@ -85,50 +84,6 @@ __global__ __launch_bounds__(256) void signed_row_kernel(int H, int W, const uns
         }
         out[x] = fg ? -best : best;
     }
-}
-
-__device__ __forceinline__ int wave_max_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-    return v;
-}
-
-// grid (ceil(HW / 2048), N * K), 256 threads.  mx[plane] = {max d2 over foreground, max d2 over background}, zeroed before
-__global__ __launch_bounds__(256) void planemax_kernel(long HW, const int* __restrict__ s2, const int* __restrict__ flags,
-                                                      int* __restrict__ mx) {
-    const int plane = blockIdx.y;
-    if (flags[plane] != 1) return;
-    const int* p = s2 + (long)plane * HW;
-    int pos = 0, neg = 0;
-    const long e0 = (long)blockIdx.x * MAX_PER_BLOCK + threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < MAX_PER_BLOCK / 256; ++j) {
-        const long e = e0 + j * 256;
-        const int v = e < HW ? p[e] : 0;
-        pos = max(pos, -v);
-        neg = max(neg, v);
-    }
-    pos = wave_max_i32(pos);
-    neg = wave_max_i32(neg);
-    if ((threadIdx.x & 63) == 0) {
-        if (pos > 0) atomicMax(&mx[plane * 2], pos);
-        if (neg > 0) atomicMax(&mx[plane * 2 + 1], neg);
-    }
-}
-
-// grid (ceil(HW / 256), N * K)
-__global__ __launch_bounds__(256) void normalise_kernel(long HW, const int* __restrict__ s2, const int* __restrict__ flags,
-                                                       const int* __restrict__ mx, float* __restrict__ sdf) {
-    const int plane = blockIdx.y;
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= HW) return;
-    float r = 0.f;
-    if (flags[plane] == 1) {
-        const int v = s2[(long)plane * HW + e];
-        if (v > 0) r = (float)(sqrt((double)v) / sqrt((double)mx[plane * 2 + 1]));
-        else if (v < -1) r = (float)-(sqrt((double)-v) / sqrt((double)mx[plane * 2]));       // v == -1: the inner boundary, 0
-    }
-    sdf[(long)plane * HW + e] = r;
 }
 
 }  // namespace

@@ -3,14 +3,16 @@
 
 Same command line (flag names and defaults of test.py:19-32; `--dataset` also accepts BUSI, which the reference
 trains but does not list here); additive flags: --synthetic, --data_root, --test_batches, --backend_dtype, --seed, --surface_metrics,
---save_dir, --save_img_mode, --post_process.  Loads
+--save_dir, --save_img_mode, --post_process, --volume_metrics, --case_pattern, --voxelspacing.  Loads
 `../model/<dataset>/<save_name>/unet_avg_dice_best_model.pth` (a plain state_dict with the reference's keys, test.py:241)
 and prints the per-domain and mean Dice of ustrun.evaluate.validate; `--surface_metrics 1` adds the reference's
 dc / jc / hd / asd lines (test.py:117-136,160-176), computed on the device instead of with medpy.  `--save_img` writes the
 reference's one picture per test image (test.py:110-113) under ./img/save (or --save_dir), rendered on the device
 (ustrun/render.py); `--save_img_mode contour` draws the library's other view, prediction against ground truth.
 `--post_process 1` runs every part of the prediction through the reference's post_processing (dataloaders/utils.py:193-204) on the
-device before it is measured or drawn.  Batches come from the seeded synthetic generator, or with --synthetic 0 from the test splits under --data_root (ustrun/datasets.py).
+device before it is measured or drawn.  `--volume_metrics 1 --case_pattern RE [--voxelspacing z,y,x]` (with --synthetic 0) also groups
+every domain's test slices into cases by `re.match(RE, name).group(1)`, stacks each case's predictions to a volume on the device and logs
+medpy's dc / jc / hd95 / asd / assd per case volume, averaged per domain (ustrun.evaluate.validate_volumes).  Batches come from the seeded synthetic generator, or with --synthetic 0 from the test splits under --data_root (ustrun/datasets.py).
 """
 import argparse
 import logging
@@ -47,6 +49,10 @@ parser.add_argument('--save_img_mode', default='mask', choices=['mask', 'contour
                     help='--save_img: draw_mask_and_save (the reference\'s) or draw_contour_and_save')
 parser.add_argument('--post_process', type=int, default=0, choices=[0, 1],
                     help='1: fill holes and drop components below a fifth of the foreground before measuring')
+parser.add_argument('--volume_metrics', type=int, default=0, choices=[0, 1],
+                    help='1: also dc / jc / hd95 / asd / assd per case volume (needs --synthetic 0 and --case_pattern)')
+parser.add_argument('--case_pattern', type=str, default='', help='--volume_metrics: regular expression whose group 1 names the case of a slice')
+parser.add_argument('--voxelspacing', type=str, default='', help='--volume_metrics: z,y,x spacing of a voxel (default: voxel units)')
 
 DOMAINS = {"fundus": 4, "prostate": 6, "MNMS": 4, "BUSI": 1}     # test.py:209-223
 
@@ -66,6 +72,8 @@ def main(args):
     C, H, K = DATASETS[args.dataset][:3]
     H = args.image_size or H
     args.domain_num = min(args.domain_num, DOMAINS[args.dataset])
+    if args.volume_metrics and (args.synthetic or not args.case_pattern):
+        raise SystemExit("--volume_metrics 1 groups the slices of a dataset's test split: it needs --synthetic 0 and --case_pattern")
     if args.model not in ('unet', 'deeplabv2'):
         raise SystemExit("--model is 'unet' (the reference's path) or 'deeplabv2' (train.py --model deeplabv2 of this build)")
     if args.model == 'deeplabv2':
@@ -75,9 +83,15 @@ def main(args):
         model = UNet(n_channels=C, n_classes=K, dtype=args.backend_dtype).cuda()
     path = args.load_path or '../model/{}/{}/{}_avg_dice_best_model.pth'.format(args.dataset, args.save_name, args.model)
     model.load_state_dict(torch.load(path, map_location="cuda"))
-    return validate(args.dataset, model, make_loaders(args, C, H), epoch=args.lb_domain, surface_metrics=bool(args.surface_metrics),
-                    save_dir=args.save_dir if args.save_img else None, save_mode=args.save_img_mode,
-                    post_process=bool(args.post_process))
+    out = validate(args.dataset, model, make_loaders(args, C, H), epoch=args.lb_domain, surface_metrics=bool(args.surface_metrics),
+                   save_dir=args.save_dir if args.save_img else None, save_mode=args.save_img_mode,
+                   post_process=bool(args.post_process))
+    if args.volume_metrics:
+        from ustrun import datasets
+        from ustrun.evaluate import validate_volumes
+        spacing = tuple(float(v) for v in args.voxelspacing.split(',')) if args.voxelspacing else None
+        validate_volumes(args.dataset, model, datasets.test_datasets(args, H, "cuda"), args.case_pattern, spacing)
+    return out
 
 
 if __name__ == "__main__":

@@ -18,9 +18,14 @@ reference's file names, on a few host threads beside the next batches' forwards 
 `validate(..., post_process=True)` applies the reference's `post_processing` (dataloaders/utils.py:193-204: holes filled, components
 below a fifth of the foreground removed) to every part of the prediction before anything is measured or drawn, on the device
 (ustrun_post_process).  Filled parts may overlap, so from there on prediction and ground truth are float planes [N,parts,H,W].
+
+`validate_volumes` is the per-CASE form for datasets that are volumes cut into slices: the slices of a resident test pool are
+grouped into cases by a pattern over their names, each case's predictions are stacked to a volume on the device and measured with
+utils.metrics.volume_metrics (medpy's dc / jc / hd95 / asd / assd with `voxelspacing`).  `validate` does not call it.
 """
 import logging
 import os
+import re
 
 import numpy as np
 import torch
@@ -206,3 +211,62 @@ def _surface_lines(part, x):
         return ""
     line = lambda m: "".join("val_%s_%s: %f, " % (n, m, x[m][k]) for k, n in enumerate(part))
     return "\n\t" + line("dc") + "\t" + line("jc") + "\n\t" + line("hd") + "\t" + line("asd")
+
+
+def case_groups(names, case_pattern):
+    """The slices of a listing grouped into cases: name i belongs to case re.match(case_pattern, name).group(1); cases and the
+    slices inside a case keep the listing's order -> [(case, [i, ...]), ...].  ValueError for a name the pattern does not match."""
+    rx = re.compile(case_pattern)
+    groups = {}
+    for i, name in enumerate(names):
+        m = rx.match(name)
+        if m is None or not m.groups():
+            raise ValueError("case_pattern %r with one group does not match the name %r" % (case_pattern, name))
+        groups.setdefault(m.group(1), []).append(i)
+    return list(groups.items())
+
+
+VOLUME_METRICS = ("dc", "jc", "hd95", "asd", "assd")
+
+
+@torch.no_grad()
+def validate_volumes(dataset, model, ds_list, case_pattern, voxelspacing=None, log=logging.info, coalesce=64):
+    """Per-case volume metrics of a test pool (test.py --volume_metrics): ds_list holds one ustrun.datasets.ResidentDataset per
+    domain; its `names` are grouped by `case_groups`, each case's slices go through the model (up to `coalesce` per forward) and
+    `predict`, prediction and ground truth are stacked to one volume [1,(parts,)D,H,W] on the device in listing order and measured
+    with utils.metrics.volume_metrics(voxelspacing) -- medpy's binary.dc / jc / hd95 / asd / assd (train.py:306-325) on the
+    volume instead of the slice.  -> per_domain[domain][metric] = [parts] means over the domain's cases; one
+    vol_<part>_dc / jc / hd95 / asd / assd line per domain is logged.  Leaves the model in train mode, as `validate` does."""
+    from .datasets import stage_finish
+    part = PARTS[dataset]
+    kw = _part_kw(dataset)
+    dev = next(model.parameters()).device
+    model.eval()
+    per_domain = []
+    for i, ds in enumerate(ds_list):
+        cases = case_groups(ds.names, case_pattern)
+        acc = {m: np.zeros(len(part)) for m in VOLUME_METRICS}
+        for case, idx in cases:
+            preds, masks = [], []
+            for o in range(0, len(idx), coalesce):
+                sel = torch.as_tensor(idx[o:o + coalesce], device=ds.images.device)
+                x, _, y = stage_finish(ds.images[sel], None, ds.labels[sel])
+                preds.append(predict(dataset, model(x.to(dev))))
+                masks.append(decode_labels(dataset, y.to(dev)))
+            pred, mask = torch.cat(preds), torch.cat(masks)               # [D,H,W] class maps, or planes [D,parts,H,W]
+            if pred.dim() == 4:
+                pred, mask = pred.transpose(0, 1), mask.transpose(0, 1)
+            try:
+                got = metrics.volume_metrics(pred[None].contiguous(), mask[None].contiguous(), voxelspacing=voxelspacing, **kw)
+            except metrics.EmptyGroundTruth as e:
+                raise metrics.EmptyGroundTruth(0, e.part, "domain %d, case %s, " % (i + 1, case)) from None
+            for m in VOLUME_METRICS:
+                acc[m] += got[m][0]
+        dom = {m: (acc[m] / max(len(cases), 1)).tolist() for m in VOLUME_METRICS}
+        per_domain.append(dom)
+        if log:
+            log("domain%d, %d cases :\n\t%s" % (i + 1, len(cases), "\n\t".join(
+                "".join("vol_%s_%s: %f, " % (n, m, dom[m][k]) for k, n in enumerate(part)) for m in VOLUME_METRICS)))
+    model.train()
+    return per_domain
+

@@ -853,6 +853,110 @@ def signed_distance_map(mask, by_class=False, num_classes=None):
     return sdf, flags
 
 
+SURFACE3D_RECORD_I32 = 10       # USTRUN_SURFACE3D_RECORD_BYTES / 4
+
+
+def _axis_weights(weights, who):
+    w = tuple(int(v) for v in weights)
+    if len(w) != 3 or any(int(v) != v for v in weights):
+        raise RuntimeError(f"{who}: weights must be three integers (wz, wy, wx), got {weights!r}")
+    return w
+
+
+def _dist_volumes(mask, by_class, num_classes, who):
+    """`_dist_planes` with one more axis -> (mask, N, K, D, H, W)"""
+    if not torch.is_tensor(mask) or not mask.is_cuda or mask.dtype not in (torch.float32, torch.int64):
+        raise RuntimeError(f"{who}: mask must be a float32 or int64 HIP tensor, got "
+                           f"{getattr(mask, 'dtype', type(mask))} on {getattr(mask, 'device', 'the host')}")
+    if by_class:
+        if mask.dim() != 4 or num_classes is None or int(num_classes) < 1:
+            raise RuntimeError(f"{who}: by_class takes a class map [N,D,H,W] and num_classes >= 1, got {tuple(mask.shape)}, {num_classes}")
+        K = int(num_classes)
+    else:
+        if mask.dim() not in (4, 5) or mask.dtype != torch.float32:
+            raise RuntimeError(f"{who}: mask must be float32 volumes [N,(K,)D,H,W] (or a class map with by_class), got "
+                               f"{mask.dtype} {tuple(mask.shape)}")
+        K = mask.shape[1] if mask.dim() == 5 else 1
+        if num_classes is not None and int(num_classes) != K:
+            raise RuntimeError(f"{who}: num_classes {num_classes} against {K} volumes")
+    return (mask.contiguous(), mask.shape[0], K) + tuple(mask.shape[-3:])
+
+
+@torch.no_grad()
+def signed_dist2_3d(mask, by_class=False, num_classes=None, weights=(1, 1, 1)):
+    """Exact signed squared distances of every volume of `mask` (ustrun_signed_dist2_3d), the 3-D form of `signed_dist2` for
+    the volumes compute_sdf is documented for (utils/util.py:208-217, shape = (batch_size, x, y, z)): float32 volumes
+    [N,(K,)D,H,W] binarised as != 0, or with by_class an int64 / float32 class map [N,D,H,W] whose volume c is == c + 1
+    -> (s2 int32 [N,K,D,H,W], flags int32 [N,K]) on the device.  d2 = wz^2 dz^2 + wy^2 dy^2 + wx^2 dx^2 with the integer
+    `weights` (wz, wy, wx), each in 1..255 (unit weights: scipy.ndimage.distance_transform_edt's default, util.py:226-227;
+    others: its `sampling`): + d2 to the nearest foreground voxel at a background voxel, - d2 to the nearest background voxel
+    at a foreground voxel, inside the volume only; flags 0 / 1 / 2 = empty / mixed / full volume, whose voxels hold
+    +- DIST_NONE where no opposite kind exists.  No gradient; nothing waits for the device."""
+    lib = L.lib()
+    mask, N, K, D, H, W = _dist_volumes(mask, by_class, num_classes, "signed_dist2_3d")
+    wz, wy, wx = _axis_weights(weights, "signed_dist2_3d")
+    nb = lib.ustrun_signed_dist2_3d_work_bytes(N, K, D, H, W)
+    if nb < 0:
+        L.check(1, "ustrun_signed_dist2_3d_work_bytes")
+    work = torch.empty(nb, dtype=torch.uint8, device=mask.device)
+    s2 = torch.empty((N, K, D, H, W), dtype=torch.int32, device=mask.device)
+    flags = torch.empty((N, K), dtype=torch.int32, device=mask.device)
+    L.check(lib.ustrun_signed_dist2_3d(mask.data_ptr(), int(mask.dtype == torch.int64), N, K, int(bool(by_class)), D, H, W, wz, wy,
+                                       wx, work.data_ptr(), nb, s2.data_ptr(), flags.data_ptr(), stream_ptr()),
+            "ustrun_signed_dist2_3d")
+    return s2, flags
+
+
+@torch.no_grad()
+def signed_distance_map_3d(mask, by_class=False, num_classes=None):
+    """The normalised signed distance map of the reference's compute_sdf (utils/util.py:208-239) for every VOLUME of `mask`
+    (as `signed_dist2_3d` takes it, unit weights) -> (sdf float32 [N,K,D,H,W], flags int32 [N,K]) on the device: the
+    normalisation of util.py:231-234 with the maxima over the whole volume; in [-1, 0) inside, exactly 0 on the inner boundary
+    (a foreground voxel with a background 6-neighbour, util.py:228), in (0, 1] outside.  Empty and full volumes are zeros --
+    read the flags.  Not differentiable; nothing waits for the device."""
+    lib = L.lib()
+    s2, flags = signed_dist2_3d(mask, by_class, num_classes)
+    N, K, D, H, W = s2.shape
+    nb = lib.ustrun_sdf_from_dist2_3d_work_bytes(N, K, D, H, W)
+    if nb < 0:
+        L.check(1, "ustrun_sdf_from_dist2_3d_work_bytes")
+    work = torch.empty(nb, dtype=torch.uint8, device=s2.device)
+    sdf = torch.empty((N, K, D, H, W), dtype=torch.float32, device=s2.device)
+    L.check(lib.ustrun_sdf_from_dist2_3d(s2.data_ptr(), flags.data_ptr(), N, K, D, H, W, work.data_ptr(), nb, sdf.data_ptr(),
+                                         stream_ptr()), "ustrun_sdf_from_dist2_3d")
+    return sdf, flags
+
+
+def surface_metrics_3d(pred, gt, by_class=False, n_classes=1, weights=(1, 1, 1)):
+    """Per (case, part) surface-distance records of VOLUMES as int32 [N,K,10] on the device (ustrun_surface_metrics_3d): what
+    medpy's binary.hd / hd95 / asd / assd (train.py:306-325, called there on slices) take from n-dimensional masks, up to the
+    host's part (utils.metrics.volume_metrics).  pred / gt: float32 volumes [N,(K,)D,H,W] or, with by_class, class maps
+    [N,D,H,W]; borders with the 6-neighbour cross, d2 with the integer axis `weights` (wz, wy, wx) in 1..255 (medpy's
+    `voxelspacing` through utils.metrics.spacing_weights).  Record: {|border(pred)|, |border(gt)|, d2[k], d2[k+1], max d2 over
+    border(pred), max d2 over border(gt)}, then the f64 sums of sqrt(d2) over border(pred) and over border(gt) in two words
+    each."""
+    lib = L.lib()
+    pred, gt = pred.contiguous(), gt.contiguous()
+    if pred.dim() < 4 or pred.shape != gt.shape or (by_class and pred.dim() != 4) or pred.dim() > 5:
+        raise RuntimeError(f"surface_metrics_3d: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must be equal [N,(K,)D,H,W] "
+                           "(a class map [N,D,H,W] with by_class)")
+    for t, name in ((pred, "pred"), (gt, "gt")):
+        if t.dtype not in (torch.float32, torch.int64) or not t.is_cuda:
+            raise RuntimeError(f"surface_metrics_3d: {name} must be a float32 or int64 HIP tensor, got {t.dtype} on {t.device}")
+    N, (D, H, W) = pred.shape[0], pred.shape[-3:]
+    K = n_classes if by_class else (pred.shape[1] if pred.dim() == 5 else 1)
+    wz, wy, wx = _axis_weights(weights, "surface_metrics_3d")
+    nb = lib.ustrun_surface_metrics_3d_work_bytes(N, K, D, H, W)
+    if nb < 0:
+        L.check(1, "ustrun_surface_metrics_3d_work_bytes")
+    work = torch.empty(nb, dtype=torch.uint8, device=pred.device)
+    out = torch.empty((N, K, SURFACE3D_RECORD_I32), dtype=torch.int32, device=pred.device)
+    L.check(lib.ustrun_surface_metrics_3d(pred.data_ptr(), gt.data_ptr(), int(pred.dtype == torch.int64),
+                                          int(gt.dtype == torch.int64), N, K, int(bool(by_class)), D, H, W, wz, wy, wx,
+                                          work.data_ptr(), nb, out.data_ptr(), stream_ptr()), "ustrun_surface_metrics_3d")
+    return out
+
+
 def sgd_ema(p, g, v, t, lr, momentum, weight_decay, first, alpha, grad_scale=1.0):
     """Fused SGD(momentum, wd) step on flat f32 buffers + EMA teacher update (train.py:512,848,87-93)."""
     lib = L.lib()

@@ -10,6 +10,9 @@ whole masks to the host.
 part, the border sizes, the two integer order statistics of the squared surface distances and the sum of the
 prediction's distances; the square roots, numpy's linear percentile and the reference's empty-mask rules are applied here.
 
+`spacing_weights` and `volume_metrics` are the per-case form of the same metrics on volumes with `voxelspacing`
+(ustrun.functional.surface_metrics_3d), adding medpy's hd and assd.
+
 `distance_transform` is the Euclidean distance transform utils/metrics.py:52-70 means to be, computed on the device.
 
 `cal_dice`, `dice`, `WatershedCrossEntropy`, `cross_entropy2d`, `dice_loss`, `DiceLoss` and `Balanced_DiceLoss` keep the reference's
@@ -71,6 +74,65 @@ def surface_from_records(records, counts, where=""):
     asd = total / np.maximum(nbp, 1)
     empty = s == 0
     return dc, jc, np.where(empty, EMPTY_PRED_VALUE, hd), np.where(empty, EMPTY_PRED_VALUE, asd)
+
+
+def spacing_weights(voxelspacing, max_scale=64, rtol=1e-6):
+    """medpy's `voxelspacing` (z, y, x) as the integer axis weights of the device's exact metric (ustrun_surface_metrics_3d):
+    -> ((wz, wy, wx), unit) with spacing_i = weight_i * unit up to `rtol`, so that a distance is unit * sqrt(d2).
+    The smallest m <= max_scale for which every spacing_i / min(spacing) * m lies within rtol (relative) of an integer is taken;
+    weights are those integers and unit = min(spacing) / m.  ValueError when no such m exists or a weight exceeds 255.
+    Pure host code."""
+    sp = [float(v) for v in voxelspacing]
+    if len(sp) != 3 or not all(np.isfinite(v) and v > 0 for v in sp):
+        raise ValueError(f"spacing_weights: voxelspacing must be three positive numbers (z, y, x), got {voxelspacing!r}")
+    lo = min(sp)
+    for m in range(1, int(max_scale) + 1):
+        q = [v / lo * m for v in sp]
+        w = [int(round(v)) for v in q]
+        if all(abs(v - r) <= rtol * r for v, r in zip(q, w)):
+            if max(w) > 255:
+                raise ValueError(f"spacing_weights: voxelspacing {tuple(sp)} needs the weights {tuple(w)}, above the device's 255")
+            return tuple(w), lo / m
+    raise ValueError(f"spacing_weights: no scale m <= {max_scale} makes voxelspacing {tuple(sp)} / {lo} integer within {rtol}")
+
+
+def volume_metrics(pred, gt, voxelspacing=None, by_class=False, n_classes=1):
+    """medpy's binary.dc / jc / hd / hd95 / asd / assd (what the reference's test() prints per slice, train.py:306-325) per
+    CASE, on volumes and in the units of `voxelspacing` (z, y, x; None: voxels) -> dict of float64 [N,K] arrays `dc`, `jc`,
+    `hd`, `hd95`, `asd`, `assd`.  pred / gt: HIP tensors [N,(K,)D,H,W], or class maps [N,D,H,W] with by_class, as
+    ustrun.functional.surface_metrics_3d takes them.  Counts (dice_counts) and the exact integer records come from the device;
+    here: distances = unit * sqrt(d2) (spacing_weights), the percentile with `surface_from_records`' arithmetic, hd = the
+    larger of the two directions' maxima, asd = the prediction's mean, assd = the mean of both directions' means.
+    Empty prediction: 100 for the four distances (train.py:313-315); empty ground truth: EmptyGroundTruth."""
+    from ustrun import functional as F
+    weights, unit = ((1, 1, 1), 1.0) if voxelspacing is None else spacing_weights(voxelspacing)
+    if by_class:
+        cp, cg = pred, gt
+    else:                                                  # dice_counts with HW := D H W: planes [N,K,DHW,1]
+        K = pred.shape[1] if pred.dim() == 5 else 1
+        cp, cg = pred.reshape(pred.shape[0], K, -1, 1), gt.reshape(gt.shape[0], K, -1, 1)
+    cnt = np.asarray(_np(F.dice_counts(cp, cg, by_class=by_class, n_classes=n_classes)), dtype=np.int64)
+    rec = np.ascontiguousarray(_np(F.surface_metrics_3d(pred, gt, by_class=by_class, n_classes=n_classes, weights=weights)),
+                               dtype=np.int32)
+    s, g, i = cnt[..., 0], cnt[..., 1], cnt[..., 2]
+    if (g == 0).any():
+        raise EmptyGroundTruth(*np.argwhere(g == 0)[0], "volume_metrics: ")
+    dc = np.where(s + g > 0, 2.0 * i / np.maximum(s + g, 1), 0.0)
+    jc = i / (s + g - i).astype(np.float64)
+    nbp, nbg = rec[..., 0].astype(np.int64), rec[..., 1].astype(np.int64)
+    sums = np.ascontiguousarray(rec[..., 6:10]).view(np.float64)
+    pos = 0.95 * (nbp + nbg - 1).astype(np.float64)
+    t = pos - np.floor(pos)
+    a, b = unit * np.sqrt(rec[..., 2].astype(np.float64)), unit * np.sqrt(rec[..., 3].astype(np.float64))
+    hd95 = np.where(t >= 0.5, b - (b - a) * (1 - t), a + (b - a) * t)          # numpy's _lerp, as surface_from_records
+    hd = unit * np.sqrt(np.maximum(rec[..., 4], rec[..., 5]).astype(np.float64))
+    asd = unit * sums[..., 0] / np.maximum(nbp, 1)
+    assd = (asd + unit * sums[..., 1] / np.maximum(nbg, 1)) / 2.0
+    empty = s == 0
+    out = {"dc": dc, "jc": jc}
+    for name, v in (("hd", hd), ("hd95", hd95), ("asd", asd), ("assd", assd)):
+        out[name] = np.where(empty, EMPTY_PRED_VALUE, v)
+    return out
 
 
 def distance_transform(bitmap):

@@ -118,3 +118,45 @@ def compute_sdf(img_gt, out_shape):
         out[b] = neg / neg.max() - pos / pos.max()
         out[b][s2[b] == -1] = 0.0
     return out.reshape(tuple(out_shape))
+
+
+def _sdf_volumes(in_shape, out_shape):
+    """compute_sdf_volume's shapes, checked before anything touches the device -> (B, D, H, W)"""
+    in_shape, out_shape = tuple(int(d) for d in in_shape), tuple(int(d) for d in out_shape)
+    if len(in_shape) != 4 or out_shape not in (in_shape, (in_shape[0], 1) + in_shape[1:]):
+        raise ValueError(f"compute_sdf_volume: img_gt {in_shape} must be [B,D,H,W] and out_shape {out_shape} the same or "
+                         "[B,1,D,H,W]")
+    return in_shape
+
+
+def compute_sdf_volume(img_gt, out_shape):
+    """utils/util.py:208-239 for the volumes its docstring names (shape = (batch_size, x, y, z), :208-217), on the device
+    (ustrun.functional.signed_distance_map_3d): the signed distance map of every binary volume img_gt[b] (binarised as != 0),
+    normalised over the whole volume to [-1, 1] -- negative inside, 0 on the inner boundary (a foreground voxel with a
+    background 6-neighbour), positive outside; all zeros for an empty volume, as the reference leaves it.  `compute_sdf` keeps
+    its planes; volumes come in under this name.
+      numpy [B,D,H,W] (any integer or bool dtype) -> float64 ndarray of out_shape from the device's exact integer squared
+        distances, square roots and quotients in float64 as the reference takes them.  A volume with no background, where the
+        reference divides 0 / 0, raises ValueError naming the sample.
+      HIP tensor [B,D,H,W] -> float32 HIP tensor of out_shape, no host trip and no wait; a full volume gives zeros there.
+    out_shape is [B,D,H,W] or [B,1,D,H,W]."""
+    B, D, H, W = _sdf_volumes(img_gt.shape, out_shape)
+    from ustrun import functional as F
+    if torch.is_tensor(img_gt):
+        if not img_gt.is_cuda:
+            raise TypeError("compute_sdf_volume: a tensor must live on the device (pass a numpy array for host data)")
+        sdf, _ = F.signed_distance_map_3d((img_gt != 0).float())
+        return sdf.reshape(tuple(out_shape))
+    mask = np.asarray(img_gt) != 0
+    s2, flags = F.signed_dist2_3d(torch.from_numpy(mask.astype(np.float32)).cuda())
+    s2, flags = s2.cpu().numpy()[:, 0].astype(np.int64), flags.cpu().numpy()[:, 0]
+    if (flags == F.PLANE_FULL).any():
+        b = int(np.argmax(flags == F.PLANE_FULL))
+        raise ValueError(f"compute_sdf_volume: sample {b} has no background voxel: its signed distance map is undefined "
+                         "(the reference divides 0 / 0 here)")
+    out = np.zeros((B, D, H, W), np.float64)
+    for b in np.flatnonzero(flags == F.PLANE_MIXED):
+        pos, neg = np.sqrt(np.maximum(-s2[b], 0).astype(np.float64)), np.sqrt(np.maximum(s2[b], 0).astype(np.float64))
+        out[b] = neg / neg.max() - pos / pos.max()
+        out[b][s2[b] == -1] = 0.0
+    return out.reshape(tuple(out_shape))
