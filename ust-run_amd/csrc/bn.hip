@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void bn_stat_stage1_kernel(float* stat, int ro
     if (rg < 2 && c < C) {                   // rg 0 -> sum into row r0, rg 1 -> sum of squares into row r0+1
         double v = 0.0;
         for (int k = 0; k < 8; ++k) v += red[rg][k][cl];
-        const float hi = (float)v, lo = (float)(v - (double)hi);
+        const float hi = (float)v, lo = __builtin_isfinite(hi) ? (float)(v - (double)hi) : 0.f;      // (an inf sum stays inf: inf - inf would park a NaN)
         stat[((long)(r0 + rg) * 2 + 0) * C + c] = hi;
         stat[((long)(r0 + rg) * 2 + 1) * C + c] = lo;
     }
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void bn_stat_fused_kernel(float* stat, int row
         if (rg < 2) {
             double v = 0.0;
             for (int k = 0; k < 8; ++k) v += red[rg][0][k][cl];
-            const float hi = (float)v, lo = (float)(v - (double)hi);
+            const float hi = (float)v, lo = __builtin_isfinite(hi) ? (float)(v - (double)hi) : 0.f;
             // write-through (sc1) stores, drained by every storing wave before the barrier in front of the ticket: no agent
             // release -- that is a write-back of the XCD's L2 (MI355X_MICROARCH.md, fence table), which the convolution has
             // just filled with dirty output lines: with it this kernel cost the step 0.6 ms MORE than the two launches
