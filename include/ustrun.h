@@ -585,6 +585,36 @@ int ustrun_surface_metrics_3d(const void* pred, const void* gt, int pred_is_i64,
                               int D, int H, int W, int wz, int wy, int wx, void* work, int64_t work_bytes, void* out,
                               ustrun_stream_t s);
 
+/* ---- post-processing of a binary prediction as a VOLUME [D][H][W] (csrc/components3d.hip): the 3-D twin of
+ * ustrun_post_process.  The reference's dataloaders/utils.py:193-204 (post_processing) is written n-dimensionally --
+ * scipy.ndimage.binary_fill_holes, skimage.measure.label and np.sum take a volume as readily as a plane -- and on the stacked
+ * slices of a case it means something else than slice by slice: a ring repeated in every slice is a tube open at both ends and
+ * stays open, a stray blob is weighed against the whole case.  pred as ustrun_post_process reads it, with D * H * W voxels where
+ * that has H * W pixels: f32 [N,K,D,H,W] binarised as (x != 0) (by_class = 0), or a class map [N,D,H,W], int64 or f32, whose
+ * part c is (x == c + 1) (by_class = 1); out: f32 {0,1} [N,K,D,H,W], never a class map.  For ONE volume P, background outside:
+ *   1 fill_holes != 0: a background voxel is a hole when no path of 6-neighbour (face) steps through background leads from it to
+ *     a face of the volume (binary_fill_holes, default structure generate_binary_structure(3, 1)); F = P | holes.  Every voxel
+ *     of slices 0 and D - 1 touches the outside: a volume with D <= 2 gains nothing, a tube along any axis gains nothing; six
+ *     voxels that touch only by edges (an octahedron) do enclose their centre.  Otherwise F = P.
+ *   2 the components of F with 26-connectivity (skimage.measure.label's default for a 3-D array, connectivity = ndim): two voxels
+ *     touching by a corner are one component; total = |F|, counted after filling.
+ *   3 component c is removed when share_den * |c| < share_num * total, in 64-bit integers.  The reference's |c| / total < 0.2 in
+ *     f64 is share 1 / 5 exactly for total <= 2^27 (a ratio below 1/5 is at least 1 / (5 total) below it, and an exact fifth
+ *     rounds to the literal 0.2).  share_num = 0 removes nothing; total = 0 gives the empty volume.
+ *   4 largest != 0 (not in the reference; the rule most 3-D pipelines apply): only the largest component of F stays, among equal
+ *     sizes the one whose smallest voxel index (z * H + y) * W + x is smallest.  Applied after rule 3 and independent of it: a
+ *     volume emptied by the share stays empty.  Chosen in integers, no floating point.
+ * fill_holes = 0, share_num = 0, largest = 0 only decodes pred (the ground truth's way into the same form).
+ * Refused before any launch and before any pointer is used: D, H or W outside 1..1024, D * H * W > 2^27, N * K > 32767,
+ * share_num < 0, share_den <= 0; then null pointers, a short work buffer (ustrun_post_process_3d_work_bytes: -1 + error for sizes
+ * out of range) and misaligned pointers (work 16-byte, out and pred to their element).  work is owned by the caller; everything
+ * is asynchronous on s, nothing is allocated, nothing waits for the device or reads from it; integer atomics only: equal bits
+ * on every run.                                                                                                           */
+int64_t ustrun_post_process_3d_work_bytes(int N, int K, int D, int H, int W);
+int ustrun_post_process_3d(const void* pred, int pred_is_i64, int N, int K, int by_class, int D, int H, int W,
+                           int fill_holes, int share_num, int share_den, int largest,
+                           void* work, int64_t work_bytes, float* out, ustrun_stream_t s);
+
 /* ---- SGD(momentum, weight decay) + EMA teacher over flat buffers: train.py:512,848,87-93 ------
  * g += wd*p; v = first ? g : mu*v + g; p -= lr*v; t = alpha*t + (1-alpha)*p                    */
 /* ---- dynamic loss scale of the IEEE-half path: torch.cuda.amp.GradScaler as train.py:552,842-845 uses it, on the device.
@@ -849,7 +879,9 @@ int ustrun_debug_flags(int flags);
  * bit 4 (16): ustrun_unet_backward stores the head's input gradient and runs layer 17's BatchNorm-backward apply pass over it, and
  *   runs layer 0's apply pass in front of the first convolution's weight gradient, as before those two round trips were dropped
  *   (ustrun_debug_last_backward_route reads 0) -- A/B runs and the equality tests.  The workspace is the same either way.
- *   bit 5 (32): layer 17's round trip alone, bit 6 (64): layer 0's alone -- each half timed with the other in place.           */
+ *   bit 5 (32): layer 17's round trip alone, bit 6 (64): layer 0's alone -- each half timed with the other in place.
+ * bit 7 (128): ustrun_post_process_3d unites every neighbour pair between adjacent slices, leaving none out as redundant -- A/B
+ *   runs and the test that the result does not depend on the pruning.                                                       */
 int ustrun_debug_flags2(int flags);
 /* Operator-level declaration (per calling thread; returns the previous value): while `allow` is nonzero, the convolution entry
  * points accept a batch whose LAST pass is shorter than ustrun_src_t::gN (N % gN != 0 -- the caller then owns a constants table of

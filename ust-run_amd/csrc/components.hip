@@ -22,26 +22,12 @@
 //   6 filter_kernel    out = 0 where the root's count is below the share
 // fill_holes = 0 drops 1-2, share_num = 0 drops the labelling of 3 and 4-6.  Integer atomics only (minimum, add): the forest's
 // roots are the components' smallest nodes and the counts are exact, whatever the order -- equal bits on every run.
-#include "common.h"
-#include "components.h"
+#include "components_dev.h"            // Shared, Local, fg_at
 
 namespace ustrun {
 namespace {
 
 constexpr int PP_MAX = 1024;             // H, W limit, as ustrun_surface_metrics has it
-
-// Access policy of a forest other blocks are lowering in the same launch: parents are read with relaxed agent-scope atomic
-// loads (a plain load may be served from this CU's L1 for ever; a stale value is still an older ancestor, cc::find) and lowered
-// with the agent-scope atomic minimum, which is what validates every link.
-struct Shared {
-    static __device__ __forceinline__ int load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    static __device__ __forceinline__ int lower(int* p, int v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-};
-// The same for a tile's forest in LDS, which only this block's waves touch
-struct Local {
-    static __device__ __forceinline__ int load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-    static __device__ __forceinline__ int lower(int* p, int v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-};
 
 struct PostWork {
     int* hole;       // [NK][HW + 1]  forest 1: background, 4 neighbours, node 0 = outside
@@ -62,15 +48,6 @@ PostWork post_carve(void* work, int64_t NK, int64_t H, int64_t W) {
     w.size = (int*)p; p += forest_bytes(NK, H, W);
     w.total = (int*)p;
     return w;
-}
-
-// the boolean plane of ustrun_dice_counts / ustrun_surface_metrics: (x == c + 1) of a class map, or (x != 0)
-__device__ __forceinline__ bool fg_at(const void* m, int is64, int by_class, long base, int c, long e) {
-    if (by_class) {
-        const long long v = is64 ? ((const long long*)m)[base + e] : (long long)((const float*)m)[base + e];
-        return v == c + 1;
-    }
-    return is64 ? ((const long long*)m)[base + e] != 0 : ((const float*)m)[base + e] != 0.f;
 }
 
 // grid (tiles, N * K), 256 threads: wave w takes the tile's rows w, w + 4, w + 8, w + 12.

@@ -1,5 +1,5 @@
-"""The tensor arithmetic of the reference's dataloaders/utils.py on the device: `post_processing` (:193-204, ustrun_post_process),
-`cross_entropy2d` (:128-144, ustrun_ce_map), `get_iou` / `get_dice` (:150-188, from one confusion matrix per image, ustrun_confusion)
+"""The tensor arithmetic of the reference's dataloaders/utils.py on the device: `post_processing` (:193-204, ustrun_post_process)
+and `post_processing_volume` (the same lines on a volume, ustrun_post_process_3d), `cross_entropy2d` (:128-144, ustrun_ce_map), `get_iou` / `get_dice` (:150-188, from one confusion matrix per image, ustrun_confusion)
 and the colour decoders (:78-120, ustrun_colorize), beside the host helpers `encode_segmap`, `lr_poly` and `untransform`.  There is no
 CPU fallback for the device functions: without the library or a HIP device the call raises.
 
@@ -21,6 +21,22 @@ def post_processing(prediction):
     if t.dim() != 2:
         raise ValueError("post_processing takes one 2-D plane, got shape %r" % (tuple(t.shape),))
     out = F.post_process((t != 0).to(device="cuda", dtype=torch.float32)[None, None])[0, 0]
+    if is_np:
+        return out.cpu().numpy().astype(bool)
+    return out.to(device=t.device, dtype=t.dtype)
+
+
+def post_processing_volume(prediction):
+    """One 3-D binary volume [D,H,W] (numpy array or tensor on any device; non-zero = foreground) -> what the reference's
+    post_processing computes when handed the volume, its scipy / skimage calls being n-dimensional: cavities filled (background
+    that no path of face steps leads from to a face of the volume), every 26-connected component below a fifth of the filled
+    foreground removed (ustrun_post_process_3d).  Conventions as `post_processing`, which keeps refusing anything but a plane:
+    numpy in gives a bool numpy array, a tensor a tensor of its device and dtype."""
+    is_np = not torch.is_tensor(prediction)
+    t = torch.from_numpy(np.ascontiguousarray(prediction)) if is_np else prediction
+    if t.dim() != 3:
+        raise ValueError("post_processing_volume takes one 3-D volume, got shape %r" % (tuple(t.shape),))
+    out = F.post_process_3d((t != 0).to(device="cuda", dtype=torch.float32)[None, None])[0, 0]
     if is_np:
         return out.cpu().numpy().astype(bool)
     return out.to(device=t.device, dtype=t.dtype)

@@ -3,7 +3,7 @@
 
 Same command line (flag names and defaults of test.py:19-32; `--dataset` also accepts BUSI, which the reference
 trains but does not list here); additive flags: --synthetic, --data_root, --test_batches, --backend_dtype, --seed, --surface_metrics,
---save_dir, --save_img_mode, --post_process, --volume_metrics, --case_pattern, --voxelspacing.  Loads
+--save_dir, --save_img_mode, --post_process, --volume_metrics, --case_pattern, --voxelspacing, --volume_post_process.  Loads
 `../model/<dataset>/<save_name>/unet_avg_dice_best_model.pth` (a plain state_dict with the reference's keys, test.py:241)
 and prints the per-domain and mean Dice of ustrun.evaluate.validate; `--surface_metrics 1` adds the reference's
 dc / jc / hd / asd lines (test.py:117-136,160-176), computed on the device instead of with medpy.  `--save_img` writes the
@@ -12,7 +12,10 @@ reference's one picture per test image (test.py:110-113) under ./img/save (or --
 `--post_process 1` runs every part of the prediction through the reference's post_processing (dataloaders/utils.py:193-204) on the
 device before it is measured or drawn.  `--volume_metrics 1 --case_pattern RE [--voxelspacing z,y,x]` (with --synthetic 0) also groups
 every domain's test slices into cases by `re.match(RE, name).group(1)`, stacks each case's predictions to a volume on the device and logs
-medpy's dc / jc / hd95 / asd / assd per case volume, averaged per domain (ustrun.evaluate.validate_volumes).  Batches come from the seeded synthetic generator, or with --synthetic 0 from the test splits under --data_root (ustrun/datasets.py).
+medpy's dc / jc / hd95 / asd / assd per case volume, averaged per domain (ustrun.evaluate.validate_volumes);
+`--volume_post_process 1` runs each case's stacked prediction through the reference's post_processing as a VOLUME first (cavities
+filled, components below a fifth of the case's foreground removed: ustrun_post_process_3d), 2 also keeps only each part's largest
+component.  `--post_process` keeps meaning the per-slice rule in `validate`.  Batches come from the seeded synthetic generator, or with --synthetic 0 from the test splits under --data_root (ustrun/datasets.py).
 """
 import argparse
 import logging
@@ -53,6 +56,8 @@ parser.add_argument('--volume_metrics', type=int, default=0, choices=[0, 1],
                     help='1: also dc / jc / hd95 / asd / assd per case volume (needs --synthetic 0 and --case_pattern)')
 parser.add_argument('--case_pattern', type=str, default='', help='--volume_metrics: regular expression whose group 1 names the case of a slice')
 parser.add_argument('--voxelspacing', type=str, default='', help='--volume_metrics: z,y,x spacing of a voxel (default: voxel units)')
+parser.add_argument('--volume_post_process', type=int, default=0, choices=[0, 1, 2],
+                    help='--volume_metrics: 1: post-process every case as a volume before measuring; 2: and keep its largest component only')
 
 DOMAINS = {"fundus": 4, "prostate": 6, "MNMS": 4, "BUSI": 1}     # test.py:209-223
 
@@ -74,6 +79,8 @@ def main(args):
     args.domain_num = min(args.domain_num, DOMAINS[args.dataset])
     if args.volume_metrics and (args.synthetic or not args.case_pattern):
         raise SystemExit("--volume_metrics 1 groups the slices of a dataset's test split: it needs --synthetic 0 and --case_pattern")
+    if args.volume_post_process and not args.volume_metrics:
+        raise SystemExit("--volume_post_process cleans the case volumes --volume_metrics 1 measures: it needs --volume_metrics 1")
     if args.model not in ('unet', 'deeplabv2'):
         raise SystemExit("--model is 'unet' (the reference's path) or 'deeplabv2' (train.py --model deeplabv2 of this build)")
     if args.model == 'deeplabv2':
@@ -90,7 +97,8 @@ def main(args):
         from ustrun import datasets
         from ustrun.evaluate import validate_volumes
         spacing = tuple(float(v) for v in args.voxelspacing.split(',')) if args.voxelspacing else None
-        validate_volumes(args.dataset, model, datasets.test_datasets(args, H, "cuda"), args.case_pattern, spacing)
+        validate_volumes(args.dataset, model, datasets.test_datasets(args, H, "cuda"), args.case_pattern, spacing,
+                         post_process=args.volume_post_process >= 1, largest=args.volume_post_process == 2)
     return out
 
 

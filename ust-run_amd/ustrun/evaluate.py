@@ -58,6 +58,15 @@ def post_processed(dataset, pred, mask):
     return F.post_process(pred, **kw), F.post_process(mask, fill_holes=False, min_share=None, **kw)
 
 
+def post_processed_volume(dataset, pred, mask, post_process=True, largest=False):
+    """`post_processed` for stacked cases [N,(parts,)D,H,W]: the prediction through the reference's post_processing on the whole
+    volume (post_process) and / or reduced to each part's largest component (largest), the ground truth through the plain decode
+    -> both float volumes [N, parts, D, H, W]."""
+    kw = _part_kw(dataset)
+    return (F.post_process_3d(pred, fill_holes=post_process, min_share=(1, 5) if post_process else None, largest=largest, **kw),
+            F.post_process_3d(mask, fill_holes=False, min_share=None, **kw))
+
+
 def sample_dice(dataset, pred, mask, planes=False):
     """Per-sample, per-part Dice [N, parts] from device overlap counts (utils/metrics.py:114-146 on every sample).
     planes: pred and mask are float planes [N, parts, H, W] whatever the dataset (`post_processed`)."""
@@ -230,13 +239,18 @@ VOLUME_METRICS = ("dc", "jc", "hd95", "asd", "assd")
 
 
 @torch.no_grad()
-def validate_volumes(dataset, model, ds_list, case_pattern, voxelspacing=None, log=logging.info, coalesce=64):
+def validate_volumes(dataset, model, ds_list, case_pattern, voxelspacing=None, log=logging.info, coalesce=64, post_process=False,
+                     largest=False):
     """Per-case volume metrics of a test pool (test.py --volume_metrics): ds_list holds one ustrun.datasets.ResidentDataset per
     domain; its `names` are grouped by `case_groups`, each case's slices go through the model (up to `coalesce` per forward) and
     `predict`, prediction and ground truth are stacked to one volume [1,(parts,)D,H,W] on the device in listing order and measured
     with utils.metrics.volume_metrics(voxelspacing) -- medpy's binary.dc / jc / hd95 / asd / assd (train.py:306-325) on the
     volume instead of the slice.  -> per_domain[domain][metric] = [parts] means over the domain's cases; one
-    vol_<part>_dc / jc / hd95 / asd / assd line per domain is logged.  Leaves the model in train mode, as `validate` does."""
+    vol_<part>_dc / jc / hd95 / asd / assd line per domain is logged.  Leaves the model in train mode, as `validate` does.
+
+    post_process=True: every part of the stacked prediction goes through the reference's post_processing AS A VOLUME first
+    (`post_processed_volume`: cavities filled, components below a fifth of the case's foreground removed); largest=True keeps only
+    the largest component of each part, after the share rule when both are set.  Default off: the path is the one above."""
     from .datasets import stage_finish
     part = PARTS[dataset]
     kw = _part_kw(dataset)
@@ -256,8 +270,12 @@ def validate_volumes(dataset, model, ds_list, case_pattern, voxelspacing=None, l
             pred, mask = torch.cat(preds), torch.cat(masks)               # [D,H,W] class maps, or planes [D,parts,H,W]
             if pred.dim() == 4:
                 pred, mask = pred.transpose(0, 1), mask.transpose(0, 1)
+            pred, mask, vkw = pred[None].contiguous(), mask[None].contiguous(), kw
+            if post_process or largest:
+                pred, mask = post_processed_volume(dataset, pred, mask, post_process=post_process, largest=largest)
+                vkw = {}
             try:
-                got = metrics.volume_metrics(pred[None].contiguous(), mask[None].contiguous(), voxelspacing=voxelspacing, **kw)
+                got = metrics.volume_metrics(pred, mask, voxelspacing=voxelspacing, **vkw)
             except metrics.EmptyGroundTruth as e:
                 raise metrics.EmptyGroundTruth(0, e.part, "domain %d, case %s, " % (i + 1, case)) from None
             for m in VOLUME_METRICS:

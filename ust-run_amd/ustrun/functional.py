@@ -957,6 +957,34 @@ def surface_metrics_3d(pred, gt, by_class=False, n_classes=1, weights=(1, 1, 1))
     return out
 
 
+def post_process_3d(pred, by_class=False, n_classes=1, fill_holes=True, min_share=(1, 5), largest=False):
+    """The reference's dataloaders/utils.py:193-204 `post_processing` on every (case, part) VOLUME of `pred` (taken as
+    `surface_metrics_3d` takes it: float32 [N,(K,)D,H,W], or with by_class a class map [N,D,H,W]) -> float32 {0,1} volumes
+    [N,K,D,H,W] on the device (ustrun_post_process_3d): holes filled (background that no path of face steps leads from to a face
+    of the volume), then every 26-connected component c with den * |c| < num * |filled volume| removed, min_share = (num, den);
+    None switches the removal off.  largest=True keeps only the largest component after that (ties: the one with the smallest
+    voxel index).  With fill_holes=False, min_share=None and largest=False the call only decodes `pred`.  Filled parts may
+    overlap, so the result is never a class map."""
+    lib = L.lib()
+    pred = pred.contiguous()
+    if pred.dim() < 4 or (by_class and pred.dim() != 4) or pred.dim() > 5:
+        raise RuntimeError(f"post_process_3d: pred {tuple(pred.shape)} must be [N,(K,)D,H,W] (a class map [N,D,H,W] with by_class)")
+    if pred.dtype not in (torch.float32, torch.int64) or not pred.is_cuda:
+        raise RuntimeError(f"post_process_3d: pred must be a float32 or int64 HIP tensor, got {pred.dtype} on {pred.device}")
+    N, (D, H, W) = pred.shape[0], pred.shape[-3:]
+    K = n_classes if by_class else (pred.shape[1] if pred.dim() == 5 else 1)
+    num, den = (0, 1) if min_share is None else (int(min_share[0]), int(min_share[1]))
+    nb = lib.ustrun_post_process_3d_work_bytes(N, K, D, H, W)
+    if nb < 0:
+        L.check(1, "ustrun_post_process_3d_work_bytes")
+    work = torch.empty(nb, dtype=torch.uint8, device=pred.device)
+    out = torch.empty((N, K, D, H, W), dtype=torch.float32, device=pred.device)
+    L.check(lib.ustrun_post_process_3d(pred.data_ptr(), int(pred.dtype == torch.int64), N, K, int(bool(by_class)), D, H, W,
+                                       int(bool(fill_holes)), num, den, int(bool(largest)), work.data_ptr(), nb, out.data_ptr(),
+                                       stream_ptr()), "ustrun_post_process_3d")
+    return out
+
+
 def sgd_ema(p, g, v, t, lr, momentum, weight_decay, first, alpha, grad_scale=1.0):
     """Fused SGD(momentum, wd) step on flat f32 buffers + EMA teacher update (train.py:512,848,87-93)."""
     lib = L.lib()
