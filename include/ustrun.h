@@ -615,6 +615,45 @@ int ustrun_post_process_3d(const void* pred, int pred_is_i64, int N, int K, int 
                            int fill_holes, int share_num, int share_den, int largest,
                            void* work, int64_t work_bytes, float* out, ustrun_stream_t s);
 
+/* ---- chamfer distances and binary morphology of label planes and volumes (csrc/morph.hip): the reference's GetBoundary
+ * (dataloaders/custom_transforms.py:630-647: ndimage.binary_dilation / binary_erosion with iterations = width per part, the
+ * pixels where the two differ, the parts ORed; built inside Normalize_tf, :659), scipy.ndimage.binary_opening / binary_closing,
+ * and scipy.ndimage.distance_transform_cdt, on the device.  All are thresholds or plain values of the exact integer distance to a
+ * set under metric 0 = city-block (L1; scipy's default structure generate_binary_structure(rank, 1), the cross; cdt's 'taxicab')
+ * or metric 1 = chessboard (L-inf; generate_binary_structure(rank, rank), 8 / 26 neighbours; cdt's 'chessboard'):
+ *   binary_dilation(A, iterations = w, border_value = b) = d(p, A) <= w,   the outside of the box part of A when b = 1
+ *   binary_erosion(A, iterations = w, border_value = b)  = d(p, ~A) > w,   the outside of the box part of ~A unless b = 1
+ * A voxel at index i of an axis of extent n is min(i + 1, n - i) from the outside along that axis.
+ * mask as ustrun_signed_dist2 reads it: f32 [N,K,D,H,W] binarised as (x != 0) (by_class = 0), or a class map [N,D,H,W], int64 or
+ * f32, whose part c is (x == c + 1) (by_class = 1).  rank 2: planes, D must be 1 and the slice axis is no axis (no border, no
+ * distance); rank 3: volumes, and D = 1 is a real one-slice volume, every voxel of which is 1 from the outside along z.
+ * Every entry refuses, before any launch and before any pointer is used: a rank other than 2 or 3, rank 2 with D != 1, D, H or W
+ * outside 1..1024, D * H * W > 2^27, N * K > 32767, a metric, outside, op or border_value code not listed here, width outside
+ * 1..4095; then null pointers, a short work buffer (the *_work_bytes queries: -1 + error) and misaligned pointers (work 16-byte,
+ * the rest to their element).  Asynchronous on s, nothing is allocated, nothing waits for the device; integers only, the only
+ * atomics are the integer flag words: equal bits on every run.
+ *
+ * ustrun_chamfer_dist: sd[N*K][D][H][W], int32: + d to the nearest foreground voxel at a background voxel, - d to the nearest
+ * background voxel at a foreground voxel.  outside: 0 = nothing outside the box is of either kind (distance_transform_cdt's
+ * convention), 1 = the outside is background, 2 = the outside is foreground.  flags[N*K]: 0 = empty, 1 = mixed, 2 = full (the
+ * box's own content, whatever `outside` says).  Where no voxel of the opposite kind exists and `outside` does not supply it, sd
+ * holds + USTRUN_DIST_NONE resp. - USTRUN_DIST_NONE.
+ *
+ * ustrun_morph: op 0 = dilation, 1 = erosion, 2 = opening (erosion, then dilation), 3 = closing (dilation, then erosion), 4 = band
+ * = dilation & ~erosion, GetBoundary's map of one part (custom_transforms.py:636-643).  width = scipy's iterations, 1..4095 (no
+ * distance in a legal box exceeds 3069: every larger count gives the same answer; iterating "until nothing changes", scipy's
+ * iterations < 1, is not built).  border_value 0 or 1 with scipy's meaning, handed to BOTH halves of an opening or closing as
+ * scipy does -- at the default 0 a closing therefore erodes from the box's faces.  reduce_parts != 0 ORs the K parts of an image:
+ * out is u8 {0,1} [N][D][H][W] (custom_transforms.py:646), otherwise [N*K][D][H][W].                                        */
+int64_t ustrun_chamfer_dist_work_bytes(int N, int K, int rank, int D, int H, int W);
+int ustrun_chamfer_dist(const void* mask, int mask_is_i64, int N, int K, int by_class, int rank, int D, int H, int W,
+                        int metric, int outside, void* work, int64_t work_bytes, int32_t* sd, int32_t* flags,
+                        ustrun_stream_t s);
+int64_t ustrun_morph_work_bytes(int N, int K, int rank, int D, int H, int W, int op);
+int ustrun_morph(const void* mask, int mask_is_i64, int N, int K, int by_class, int rank, int D, int H, int W,
+                 int metric, int op, int width, int border_value, int reduce_parts,
+                 void* work, int64_t work_bytes, uint8_t* out, ustrun_stream_t s);
+
 /* ---- SGD(momentum, weight decay) + EMA teacher over flat buffers: train.py:512,848,87-93 ------
  * g += wd*p; v = first ? g : mu*v + g; p -= lr*v; t = alpha*t + (1-alpha)*p                    */
 /* ---- dynamic loss scale of the IEEE-half path: torch.cuda.amp.GradScaler as train.py:552,842-845 uses it, on the device.

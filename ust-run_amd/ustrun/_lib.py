@@ -117,6 +117,10 @@ SIGNATURES = {
     "ustrun_surface_metrics_3d": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp]),
     "ustrun_post_process_3d_work_bytes": (i64, [i32, i32, i32, i32, i32]),
     "ustrun_post_process_3d": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, fp, vp]),
+    "ustrun_chamfer_dist_work_bytes": (i64, [i32, i32, i32, i32, i32, i32]),
+    "ustrun_chamfer_dist": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp]),
+    "ustrun_morph_work_bytes": (i64, [i32, i32, i32, i32, i32, i32, i32]),
+    "ustrun_morph": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp]),
     "ustrun_sgd_ema": (i32, [fp, fp, fp, fp, i64, f32, f32, f32, i32, f32, f32, vp]),
     "ustrun_amp_check": (i32, [fp, i64, fp, vp]),
     "ustrun_sgd_ema_scaled": (i32, [fp, fp, fp, fp, i64, f32, f32, f32, i32, f32, f32, fp, vp]),

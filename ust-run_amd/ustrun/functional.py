@@ -985,6 +985,148 @@ def post_process_3d(pred, by_class=False, n_classes=1, fill_holes=True, min_shar
     return out
 
 
+METRIC_TAXICAB, METRIC_CHESSBOARD = 0, 1
+MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE, MORPH_BAND = 0, 1, 2, 3, 4
+MORPH_WIDTH_MAX = 4095          # no distance in a box the kernels accept exceeds 3069: every larger count gives the same answer
+
+
+def _morph_box(mask, by_class, num_classes, who):
+    """planes [N,K,H,W] / volumes [N,K,D,H,W], or with by_class class maps [N,H,W] / [N,D,H,W] -> (mask, N, K, rank, D, H, W)"""
+    if not torch.is_tensor(mask) or not mask.is_cuda or mask.dtype not in (torch.float32, torch.int64):
+        raise RuntimeError(f"{who}: mask must be a float32 or int64 HIP tensor, got "
+                           f"{getattr(mask, 'dtype', type(mask))} on {getattr(mask, 'device', 'the host')}")
+    if by_class:
+        if mask.dim() not in (3, 4) or num_classes is None or int(num_classes) < 1:
+            raise RuntimeError(f"{who}: by_class takes a class map [N,H,W] or [N,D,H,W] and num_classes >= 1, got "
+                               f"{tuple(mask.shape)}, {num_classes}")
+        K, rank = int(num_classes), mask.dim() - 1
+    else:
+        if mask.dim() not in (4, 5) or mask.dtype != torch.float32:
+            raise RuntimeError(f"{who}: mask must be float32 planes [N,K,H,W] or volumes [N,K,D,H,W] (or a class map with by_class), "
+                               f"got {mask.dtype} {tuple(mask.shape)}")
+        K, rank = mask.shape[1], mask.dim() - 2
+        if num_classes is not None and int(num_classes) != K:
+            raise RuntimeError(f"{who}: num_classes {num_classes} against {K} parts")
+    D = mask.shape[-3] if rank == 3 else 1
+    return mask.contiguous(), mask.shape[0], K, rank, D, mask.shape[-2], mask.shape[-1]
+
+
+def _metric_code(metric, who):
+    codes = {"taxicab": METRIC_TAXICAB, "cityblock": METRIC_TAXICAB, "manhattan": METRIC_TAXICAB, "chessboard": METRIC_CHESSBOARD}
+    if metric not in codes:
+        raise RuntimeError(f"{who}: metric must be 'taxicab' (alias 'cityblock', 'manhattan') or 'chessboard', got {metric!r}")
+    return codes[metric]
+
+
+def _structure_code(structure, rank, who):
+    """None, 1 or "cross": scipy's default generate_binary_structure(rank, 1) -> the city-block metric; the rank or "full":
+    generate_binary_structure(rank, rank) -> the chessboard metric.  Nothing else is a threshold of a separable distance."""
+    if structure is None or (isinstance(structure, str) and structure == "cross"):
+        return METRIC_TAXICAB
+    if isinstance(structure, str) and structure == "full":
+        return METRIC_CHESSBOARD
+    if isinstance(structure, int) and not isinstance(structure, bool):
+        if structure == 1:
+            return METRIC_TAXICAB
+        if structure == rank:
+            return METRIC_CHESSBOARD
+        if rank == 3 and structure == 2:
+            raise RuntimeError(f"{who}: connectivity 2 in 3-D (18 neighbours) is not built: its distance is not separable per axis; "
+                               "use 1 / 'cross' (6 neighbours) or 3 / 'full' (26 neighbours)")
+    raise RuntimeError(f"{who}: structure must be None, 1 or 'cross' (the cross), or {rank} or 'full' (the full structure) for rank "
+                       f"{rank}; arbitrary structuring elements are not built, got {structure!r}")
+
+
+@torch.no_grad()
+def chamfer_distance(mask, metric="taxicab", outside=0, by_class=False, num_classes=None):
+    """Exact signed chamfer distances of every plane or volume of `mask` (ustrun_chamfer_dist): float32 [N,K,H,W] / [N,K,D,H,W]
+    binarised as != 0, or with by_class an int64 / float32 class map [N,H,W] / [N,D,H,W] whose part c is == c + 1
+    -> (sd int32 like [N,K,...], flags int32 [N,K]) on the device.  metric 'taxicab' (city-block, L1) or 'chessboard' (L-inf):
+    + d to the nearest foreground pixel at a background pixel, - d to the nearest background pixel at a foreground pixel.
+    outside 0: nothing outside the box is of either kind (scipy.ndimage.distance_transform_cdt's convention); 1: the outside is
+    background; 2: the outside is foreground.  flags 0 / 1 / 2 = empty / mixed / full; where no pixel of the opposite kind exists
+    and `outside` supplies none, sd holds +- DIST_NONE.  No gradient; nothing waits for the device."""
+    lib = L.lib()
+    mask, N, K, rank, D, H, W = _morph_box(mask, by_class, num_classes, "chamfer_distance")
+    code = _metric_code(metric, "chamfer_distance")
+    if outside not in (0, 1, 2):
+        raise RuntimeError(f"chamfer_distance: outside must be 0 (neither kind), 1 (background) or 2 (foreground), got {outside!r}")
+    nb = lib.ustrun_chamfer_dist_work_bytes(N, K, rank, D, H, W)
+    if nb < 0:
+        L.check(1, "ustrun_chamfer_dist_work_bytes")
+    work = torch.empty(nb, dtype=torch.uint8, device=mask.device)
+    box = (D, H, W) if rank == 3 else (H, W)
+    sd = torch.empty((N, K) + box, dtype=torch.int32, device=mask.device)
+    flags = torch.empty((N, K), dtype=torch.int32, device=mask.device)
+    L.check(lib.ustrun_chamfer_dist(mask.data_ptr(), int(mask.dtype == torch.int64), N, K, int(bool(by_class)), rank, D, H, W, code,
+                                    int(outside), work.data_ptr(), nb, sd.data_ptr(), flags.data_ptr(), stream_ptr()),
+            "ustrun_chamfer_dist")
+    return sd, flags
+
+
+@torch.no_grad()
+def distance_transform_cdt(mask, metric="chessboard", by_class=False, num_classes=None):
+    """scipy.ndimage.distance_transform_cdt(part, metric) of every plane or volume of `mask` (as `chamfer_distance` takes it), as
+    int32 on the device: the distance to the nearest background pixel on the foreground, 0 on the background, and -1 everywhere
+    on a part without background, which is what scipy returns for it.  Nothing waits for the device."""
+    sd, flags = chamfer_distance(mask, metric, 0, by_class, num_classes)
+    full = (flags == PLANE_FULL).view(flags.shape + (1,) * (sd.dim() - 2))
+    return torch.where(full, torch.full_like(sd, -1), (-sd).clamp_(min=0))
+
+
+def _morph(mask, op, metric, width, border_value, reduce_parts, by_class, num_classes, who):
+    lib = L.lib()
+    mask, N, K, rank, D, H, W = _morph_box(mask, by_class, num_classes, who)
+    code = metric(rank) if callable(metric) else metric
+    if int(width) != width or width < 1:
+        raise RuntimeError(f"{who}: iterations / width must be an integer >= 1, got {width!r} (scipy's iterations < 1, repeating "
+                           "until nothing changes, is not built)")
+    if border_value not in (0, 1, False, True):
+        raise RuntimeError(f"{who}: border_value must be 0 or 1, got {border_value!r}")
+    width = min(int(width), MORPH_WIDTH_MAX)
+    nb = lib.ustrun_morph_work_bytes(N, K, rank, D, H, W, op)
+    if nb < 0:
+        L.check(1, "ustrun_morph_work_bytes")
+    work = torch.empty(nb, dtype=torch.uint8, device=mask.device)
+    box = (D, H, W) if rank == 3 else (H, W)
+    out = torch.empty(((N,) if reduce_parts else (N, K)) + box, dtype=torch.uint8, device=mask.device)
+    L.check(lib.ustrun_morph(mask.data_ptr(), int(mask.dtype == torch.int64), N, K, int(bool(by_class)), rank, D, H, W, code, op,
+                             width, int(border_value), int(bool(reduce_parts)), work.data_ptr(), nb, out.data_ptr(), stream_ptr()),
+            "ustrun_morph")
+    return out
+
+
+def _binary_op(op, who):
+    @torch.no_grad()
+    def fn(mask, structure=None, iterations=1, border_value=0, by_class=False, num_classes=None):
+        return _morph(mask, op, lambda rank: _structure_code(structure, rank, who), iterations, border_value, False, by_class,
+                      num_classes, who).view(torch.bool)
+    fn.__name__ = fn.__qualname__ = who
+    fn.__doc__ = (f"scipy.ndimage.{who}(part, structure, iterations, border_value=border_value) of every plane or volume of `mask` "
+                  "(ustrun_morph; float32 [N,K,H,W] / [N,K,D,H,W] binarised as != 0, or with by_class a class map [N,H,W] / "
+                  "[N,D,H,W] whose part c is == c + 1) -> bool like [N,K,...] on the device.  structure: None, 1 or 'cross' = "
+                  "generate_binary_structure(rank, 1), scipy's default; the rank or 'full' = generate_binary_structure(rank, rank); "
+                  "anything else raises.  iterations >= 1 (counts past 4095 are clamped: they give the same answer).  border_value "
+                  "has scipy's meaning and, as in scipy, goes to both halves of an opening or closing.  Nothing waits for the device.")
+    return fn
+
+
+binary_dilation = _binary_op(MORPH_DILATE, "binary_dilation")
+binary_erosion = _binary_op(MORPH_ERODE, "binary_erosion")
+binary_opening = _binary_op(MORPH_OPEN, "binary_opening")
+binary_closing = _binary_op(MORPH_CLOSE, "binary_closing")
+
+
+@torch.no_grad()
+def boundary_band(mask, width=5, structure=None, reduce_parts=True, by_class=False, num_classes=None):
+    """The reference's GetBoundary map (dataloaders/custom_transforms.py:630-647) of every image of `mask` (as `binary_dilation`
+    takes it): per part, the pixels where the dilation and the erosion by `width` steps differ (border_value 0, as the reference
+    calls scipy); reduce_parts ORs the K parts of an image (custom_transforms.py:646) -> uint8 {0,1} [N,...] on the device,
+    otherwise [N,K,...].  Nothing waits for the device."""
+    return _morph(mask, MORPH_BAND, lambda rank: _structure_code(structure, rank, "boundary_band"), width, 0, reduce_parts, by_class,
+                  num_classes, "boundary_band")
+
+
 def sgd_ema(p, g, v, t, lr, momentum, weight_decay, first, alpha, grad_scale=1.0):
     """Fused SGD(momentum, wd) step on flat f32 buffers + EMA teacher update (train.py:512,848,87-93)."""
     lib = L.lib()
